@@ -2,7 +2,8 @@
 """Headline benchmark: R2D2 learner steps/s on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config atari57|reference|...]
-                    [--dtype fp32|bf16] [--target-mode fixed|shifted|reference] [--profile-phases]
+                    [--dtype fp32|bf16] [--target-mode fixed|shifted|reference]
+                    [--dump-outputs DIR] [--full] [--profile-phases]
 
 * Config (default ``atari57``): the R2D2 paper shapes -- batch 64 sequences of 80 steps
   (burn-in 40 + learning 40), n-step 5, value rescaling, IS weights, centered RMSprop -- on the
@@ -31,6 +32,13 @@
 * Timing: W untimed warmup steps, then exactly K steps bracketed by barrier + synchronize on
   both sides; the max over ranks is reported by rank 0 as one JSON line.  The persistent
   kernels' error word is read after the timed loop: a non-zero word fails the run (exit 3).
+* A plain run does only that: set up, warm up, time the K steps, print the line.  ``--full`` adds
+  everything else the benchmark measures (today the per-phase timing of ``--profile-phases``).
+* ``--dump-outputs DIR`` writes what the last timed step left a caller of the learner, as
+  ``DIR/<name>.npy`` (float32): loss, Q(s, .) and |TD error| of its batch, online and target
+  weights, both optimizer moments and the replay priorities (``dump_outputs``).  Model seed,
+  replay contents and the device sampling RNG are fixed by the arguments, so two builds run with
+  the same arguments see the same inputs.
 """
 from __future__ import annotations
 
@@ -54,6 +62,48 @@ def data_label(cfg) -> str:
             f"in HBM replay, random-init weights")
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # all of --dump-outputs together (float32)
+
+
+def dump_cap(sizes, budget: int):
+    """Largest element count an array may keep so that ``sum(min(n, cap) for n in sizes)`` stays
+    within ``budget`` elements; None when everything fits whole."""
+    sizes = sorted(sizes)
+    left = budget
+    for i, n in enumerate(sizes):
+        share = left // (len(sizes) - i)
+        if n > share:
+            return share
+        left -= n
+    return None
+
+
+def dump_outputs(path: str, eng, replay) -> None:
+    """The last step's results as ``path/<name>.npy`` (float32).  Arrays are written whole while
+    the total fits DUMP_BUDGET_BYTES; beyond it the largest ones are cut to an equal share, each
+    to a fixed seeded sample of its elements (sorted indices of ``default_rng(0)``)."""
+    import numpy as np
+    n_learn = eng.Ll * eng.B
+    arrays = {
+        "loss": eng.loss,
+        "q_online": eng.q_on[:n_learn],
+        "td_abs": eng.td_abs[:n_learn],
+        "online_params": eng.master,
+        "target_params": eng.target,
+        "opt_a": eng.opt_a,
+        "opt_b": eng.opt_b,
+        "replay_priority": replay.priority,
+    }
+    cap = dump_cap([t.numel() for t in arrays.values()], DUMP_BUDGET_BYTES // 4)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if cap is not None and a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -67,6 +117,12 @@ def main(argv=None):
     ap.add_argument("--profile-phases", action="store_true",
                     help="after the timed run, time each phase of 5 eager steps with HIP events "
                          "(+ roctx ranges) and add them to the JSON line under 'phases_ms'")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's results (loss, Q values, "
+                         "|TD|, weights, optimizer moments, priorities) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures beyond the headline figure: today "
+                         "the per-phase timing of --profile-phases")
     ap.add_argument("--force-dp", action="store_true",
                     help="rehearsal under torchrun at ONE rank: the data-parallel step (segmented "
                          "graphs, RCCL all-reduces on the comm stream, CU reservation, shard-stats "
@@ -153,8 +209,10 @@ def main(argv=None):
     ms = dt / args.steps * 1e3
     opt_steps = args.steps / dt
     loss = eng.loss_value()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, replay)
     phases = None
-    if args.profile_phases:
+    if args.profile_phases or args.full:
         timer = PhaseTimer()
         for _ in range(5):
             eng.step_eager(timer=timer)
