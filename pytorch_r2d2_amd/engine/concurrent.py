@@ -19,9 +19,17 @@ native path both roles live in one process per GPU and run SIMULTANEOUSLY on dis
   writes rows, so the actor never touches them (``actor.hip`` deferred mode): start marks and
   clears go to a pending list (two lists, round parity) that the learner's stream applies in front
   of its next step (``replay.hip`` apply_pending_kernel + dirty-list tree repair).  Rows are
-  invalidated ``lookahead >= M`` steps ahead of the write head, so a row written in round ``r`` had
-  its starts cleared in a round ``<= r - 1``, applied before learner step ``r`` sampled; learner step
-  ``r - 1`` (which may still have sampled them) finished before actor round ``r`` started;
+  invalidated ``lookahead`` steps ahead of the write head.  Plain learner step: ``lookahead >= M``,
+  so a row written in round ``r`` had its starts cleared in a round ``<= r - 1``, applied before
+  learner step ``r`` sampled; learner step ``r - 1`` (which may still have sampled them) finished
+  before actor round ``r`` started.  Hoisted learner step (``learner.hoist``, the default): step
+  ``r``'s batch is sampled INSIDE step ``r - 1``, after round ``r - 2``'s pending list was applied
+  but before round ``r - 1``'s, and trained on beside round ``r``.  So ``lookahead >= 2M``: a row
+  written in round ``r`` had its starts cleared in a round ``<= r - 2``, applied in front of step
+  ``r - 1``, inside which step ``r`` sampled; rows written in round ``r - 1`` were cleared in a
+  round ``<= r - 3``.  The default lookahead is ``2M + 2`` (``M + 2`` for a plain engine), a
+  smaller explicit one is refused, and the driver sets ``engine.writes_covered`` so the engine
+  keeps its pre-sampled batches although the actor writes between its steps;
 * **weights** -- the actor reads its OWN packed copy.  Every ``publish_interval`` learner steps the
   learner's stream copies master + target into a staging slot behind its step, and the actor's
   stream re-packs that slot at the start of its next round (after the event wait), so the actor
@@ -47,9 +55,16 @@ class ConcurrentDriver:
         if engine.replay is not rp:
             raise ValueError("actor and learner must share one HBM replay")
         self.M = M = int(steps_per_round)
-        self.D = D = int(lookahead) if lookahead else M + 2
+        # rounds between the clear of a row's starts and its overwrite: 1, or 2 when the engine
+        # samples step r's batch inside step r - 1 (see the module docstring)
+        need = 2 * M if engine.hoist else M
+        self.D = D = int(lookahead) if lookahead else need + 2
         if D < M:
             raise ValueError("lookahead must be >= steps_per_round")
+        if D < need:
+            raise ValueError(f"lookahead {D} < 2 * steps_per_round = {need}: the hoisted learner step "
+                             "samples a round ahead (use learner.hoist=False for a shorter lookahead)")
+        engine.writes_covered = bool(engine.hoist)
         self.P = int(publish_interval or engine.cfg.learner.publish_interval)
         dev = rp.device
         E, n, W = actor.E, actor.n, actor.T + actor.n
@@ -91,6 +106,8 @@ class ConcurrentDriver:
         actor.step(parity=0)
         self._apply(0)
         torch.cuda.synchronize(dev)
+        # a batch the engine sampled before the switch-over knew nothing of the lookahead
+        engine.invalidate_hoist()
         self.apply_graphs = None
         if capture and dev.type == "cuda":
             with torch.cuda.stream(self.s_act):

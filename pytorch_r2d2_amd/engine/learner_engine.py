@@ -206,10 +206,6 @@ class LearnerEngine:
         self.graph = None
         self.stats: Dict[str, float] = {}
         self._alloc()
-        if d.type == "cuda":
-            # the BPTT packed two groups per XCD only beside the hoisted torso frames (alone it
-            # runs faster one group per XCD: 100 vs 113 us, profiles/r06_hoist_bptt_placement.txt)
-            kernels().r2_lstm_bwd_xcd_pairs(1 if self.hoist else 0)
         # world 1 (no gradient all-reduce, no clipping): the torso backward's slab reduction rides
         # on the optimizer launch (r2_rmsprop_pack_slab: one launch fewer); the torso bucket is the
         # master's tail, so the update's quad loop stops at its first quad
@@ -295,6 +291,8 @@ class LearnerEngine:
         self.h0 = {k: z(B, H, dt=act_dt) for k in ("on", "tg", "nx")}
         self.c0 = {k: z(B, H) for k in ("on", "tg", "nx")}
         self.hoist = self._hoist_ok()
+        self.hoisted_steps = 0        # steps that trained on the batch the previous step sampled
+        self.writes_covered = False   # a driver vouches for its replay writes (_hoist_fresh)
         # the sampled batch (starts / probs / rows / stored states) in two sets: the hoisted step
         # k samples step k+1's batch into the other set while its own kernels still read set k % 2
         self._sets = [dict(starts=self.starts, probs=self.probs, rows=self.rows, h0=self.h0, c0=self.c0)]
@@ -441,7 +439,11 @@ class LearnerEngine:
     # the queue.  Every frame is computed by the same kernel code from the same operands, the
     # sample uses the same device step counter, and the target packs are only used when no
     # target sync happened in between (the host knows the sync steps: the update is captured with
-    # the due decision baked in), so the step is bit-identical to the plain one.
+    # the due decision baked in), so the step is bit-identical to the plain one -- as long as the
+    # replay does not change between the hoisted sample and the step that trains on it.  A batch
+    # sampled before a replay write is dropped (_hoist_fresh: HBMReplay.total_written moved), and
+    # that step samples at its start like the plain one; only a driver that keeps its writes away
+    # from pending batches (engine/concurrent.py) sets ``writes_covered``.
     def _hoist_ok(self) -> bool:
         lc = self.cfg.learner
         return bool(lc.hoist and self.sp and self.fused_torso and not self.sp_lib
@@ -457,9 +459,21 @@ class LearnerEngine:
 
     def invalidate_hoist(self) -> None:
         """Drop the batch the previous step sampled (and the target frames it computed) for the
-        next one: call after changing the replay (ingest, actor writes) or the weights between
-        steps.  The next step samples at its start, as the plain step does."""
+        next one: call after changing the weights between steps, or the replay through a path
+        that does not count its rows in ``HBMReplay.total_written`` (the counted writers -- actor
+        steps, ingests -- are noticed by ``_hoist_fresh``).  The next step samples at its start,
+        as the plain step does."""
         self._hoist_ready = False
+
+    def _hoist_fresh(self) -> bool:
+        """The previous step sampled this step's batch AND the replay has not been written since
+        (every host-side writer bumps ``HBMReplay.total_written``): a batch sampled before a write
+        may hold windows the write overwrote, and came from a tree the plain step would not have
+        used.  ``writes_covered``: a driver whose writes stay clear of every batch that may
+        still be pending (engine/concurrent.py: lookahead >= 2 rounds) vouches for them."""
+        return bool(getattr(self, "_hoist_ready", False)
+                    and (self.writes_covered
+                         or getattr(self, "_hoist_gen", None) == self.replay.total_written))
 
     def _due(self, k: int) -> bool:
         iv = int(self.cfg.learner.target_update_interval)
@@ -523,6 +537,13 @@ class LearnerEngine:
                                                       stream_handle(side)), "torso_fwd_sp (hoisted)")
         return side
 
+    def _set_bptt_placement(self) -> None:
+        """In front of every tagged BPTT launch, like set_stop / set_dz: the recurrence packed two
+        groups per XCD only beside the hoisted torso frames (alone it runs faster one group per
+        XCD: 100 vs 113 us, profiles/r06_hoist_bptt_placement.txt).  The kernel library keeps one
+        process-wide switch, so each launch sets it from the launching engine's own value."""
+        kernels().r2_lstm_bwd_xcd_pairs(1 if self.hoist else 0)
+
     def _bptt_pairs(self) -> bool:
         """The hoisted BPTT packs its recurrence groups two per XCD (lstm_persist.hip xcd_map 3,
         hidden / 16 = 16 workgroups a group; alone it runs faster one group per XCD, 97 vs 105
@@ -583,13 +604,15 @@ class LearnerEngine:
             self._dev_step_off = int(self.replay.step.item()) - k
         due = self._due(k + self._dev_step_off)
         p = k & 1
-        inm = "H" if getattr(self, "_hoist_ready", False) else "P"
+        inm = "H" if self._hoist_fresh() else "P"
         if self.graph:
             self._use_set(p)
             self._hgraphs[(p, inm, due)].replay()
         else:
             self._hoist_body(p, inm, due)
+        self.hoisted_steps += inm == "H"
         self._hoist_ready = True
+        self._hoist_gen = self.replay.total_written    # the replay the next batch was sampled from
         self.steps_done += 1
 
     def _chunk_len(self) -> int:
@@ -598,7 +621,8 @@ class LearnerEngine:
     def run_steps(self, n: int) -> None:
         """``n`` learner steps, the same work and results as ``n`` calls of ``step``.  In the
         hoisted graph mode a run of ``learner.graph_chunk`` steps that starts at an even step,
-        follows a hoisted step and has no target sync inside replays as ONE captured graph
+        follows a hoisted step with no replay write since (``_hoist_fresh``; writes happen between
+        calls, so never inside a chunk) and has no target sync inside replays as ONE captured graph
         (the hoisted bodies back to back on the same streams): the ~5 us boundary between two
         graph replays (profiles/r06_step_timeline.txt) is paid once per chunk."""
         m = self._chunk_len()
@@ -606,13 +630,15 @@ class LearnerEngine:
             k = self.steps_done
             off = getattr(self, "_dev_step_off", None)
             if (n >= m and m > 1 and self.graph and getattr(self, "_cgraph", None) is not None
-                    and (k & 1) == 0 and getattr(self, "_hoist_ready", False) and off is not None
+                    and (k & 1) == 0 and self._hoist_fresh() and off is not None
                     and not any(self._due(k + j + off) for j in range(m))):
                 self._use_set(0)
                 self._cgraph.replay()
                 self.chunks_run = getattr(self, "chunks_run", 0) + 1
                 self._use_set((m - 1) & 1)
                 self._hoist_due = False
+                self.hoisted_steps += m
+                self._hoist_gen = self.replay.total_written
                 self.steps_done += m
                 n -= m
             else:
@@ -1037,6 +1063,7 @@ class LearnerEngine:
         check(k.r2_lstm_bwd_set_stop(ptr(self.tq[2:]) if self.hoist else 0,
                                      max(0, self.Ll - int(lc.hoist_stop_lead)), 0),
               "lstm_bwd_set_stop")
+        self._set_bptt_placement()
         if side_hg:
             rc = k.r2_lstm_bwd_tag_sp_hg(*bptt, *hg, s)   # >= 0: bit 0 = head grads done here
         else:
@@ -1220,6 +1247,7 @@ class LearnerEngine:
                     ptr(pk["w_hhT"]), ptr(self.dgates), B, T, Lb, H, ptr(self.ctr), ptr(self.err),
                     ptr(self.ring_b), ptr(self.bias_ws), ptr(self.gate_perm_i32),
                     ptr(L.view(g, "lstm.bias_ih")), ptr(L.view(g, "lstm.bias_hh"))]
+            self._set_bptt_placement()
             rc = k.r2_lstm_bwd_tag(*base, *self._hg_job, s)
             if rc in (-6, -10):   # not enough idle workgroups for the side job: recurrence alone
                 rc = k.r2_lstm_bwd_tag(*base, *([0] * 11), s)

@@ -229,7 +229,7 @@ def test_cu_masked_streams_partition_the_chip():
         sl.close()
 
 
-def _concurrent_setup(E=16, cap_e=512, M=2, masked=True, **over):
+def _concurrent_setup(E=16, cap_e=512, M=2, masked=True, lookahead=None, driver=True, **over):
     from pytorch_r2d2_amd.actor_batched import BatchedActor, engine_weights
     from pytorch_r2d2_amd.engine.concurrent import ConcurrentDriver
     from pytorch_r2d2_amd.engine.learner_engine import LearnerEngine
@@ -250,44 +250,58 @@ def _concurrent_setup(E=16, cap_e=512, M=2, masked=True, **over):
         actor.step()
     eng.capture(warmup=1)
     actor.n_workers = na
-    drv = ConcurrentDriver(eng, actor, steps_per_round=M,
-                           actor_stream=sa.stream if sa else None,
-                           learner_stream=sl.stream if sl else None)
+    drv = None
+    if driver:
+        drv = ConcurrentDriver(eng, actor, steps_per_round=M, lookahead=lookahead,
+                               actor_stream=sa.stream if sa else None,
+                               learner_stream=sl.stream if sl else None)
     return cfg, rp, eng, actor, drv, (sa, sl)
 
 
-@pytest.mark.parametrize("masked", [True, False], ids=["cu_masked", "shared_chip"])
-def test_concurrent_driver_never_samples_rows_being_written(masked):
-    cfg, rp, eng, actor, drv, streams = _concurrent_setup(masked=masked)
-    B, Tn = cfg.learner.batch_size, cfg.replay.seq_len + cfg.replay.n_step
-    R = 120
+@pytest.mark.parametrize("masked,M,R", [(True, 2, 120), (False, 2, 120), (True, 4, 100), (False, 4, 100)],
+                         ids=["cu_masked", "shared_chip", "cu_masked-M4", "shared_chip-M4"])
+def test_concurrent_driver_never_samples_rows_being_written(masked, M, R):
+    """The default path: the hoisted learner step, which samples step r's batch inside step
+    r - 1.  The rows written between that sampling and the training are those of actor rounds
+    r - 1 and r (round r alone for a step that sampled at its own start); no sampled window may
+    meet them (engine/replay_check.py), at the driver's default lookahead."""
+    from pytorch_r2d2_amd.engine.replay_check import (bootstrap_violations, check_windows,
+                                                      ring_offsets)
+    cfg, rp, eng, actor, drv, streams = _concurrent_setup(masked=masked, M=M)
+    assert eng.hoist and eng.writes_covered and drv.D == 2 * M + 2
+    B = cfg.learner.batch_size
     hist = torch.zeros(R, B, dtype=torch.int32, device=DEV)
+    taken = []          # eng.hoisted_steps after every learner step
 
     def log_starts(i):
         if i < R:
             hist[i].copy_(eng.starts)
+            taken.append(eng.hoisted_steps)
     drv.on_learner_step = log_starts
     drv.run(R)
     drv.finish()
     drv.check_errors()
     starts = hist.cpu().numpy()
     done = rp.done.cpu().numpy()
-    cap_e, M, T = rp.cap_e, drv.M, cfg.replay.seq_len
+    cap_e, T, n = rp.cap_e, cfg.replay.seq_len, cfg.replay.n_step
+    assert drv.M == M and drv.rounds == R
     assert drv.rounds * M + drv.heads[0] < cap_e          # no wrap: rows keep their round's data
-    n_ext = 0
+    # every step but the first trained on the batch the step before it sampled
+    pre = [b - a == 1 for a, b in zip([0] + taken[:-1], taken)]
+    assert pre == [False] + [True] * (R - 1)
+    written = []
     for r in range(R):
-        written = {(drv.heads[r] + j) % cap_e for j in range(M)}
-        for s in starts[r]:
-            off, base = s % cap_e, s - s % cap_e
-            window = {(off + t) % cap_e for t in range(T)}
-            assert not (window & written), (r, s)
-            # the n bootstrap frames past the window may be the next episode's first rows (being
-            # written): only for a final start, whose last learning row is terminal (masked)
-            ext = {(off + t) % cap_e for t in range(T, Tn)}
-            if ext & written:
-                n_ext += 1
-                assert done[base + (off + T - 1) % cap_e] == 1, (r, s)
-    print("samples whose masked bootstrap frames were being written:", n_ext)
+        w = ring_offsets(drv.heads[r], M, cap_e)
+        if pre[r]:
+            w = np.concatenate([ring_offsets(drv.heads[r - 1], M, cap_e), w])
+        written.append(w)
+    torn, boot = check_windows(starts, cap_e, T, n, written)
+    assert not torn, torn[:8]
+    # the n bootstrap frames past the window may be the next episode's first rows (being
+    # written): only for a final start, whose last learning row is terminal (masked)
+    bad = bootstrap_violations(boot, done, cap_e, T)
+    assert not bad, bad[:8]
+    print("samples whose masked bootstrap frames were being written:", len(boot))
     # weights: published every 5 learner steps; the actor's copy is the last published master
     assert drv.version == R // 5
     torch.testing.assert_close(drv.w_on.flat, drv.stage_on, rtol=0, atol=0)
@@ -297,6 +311,25 @@ def test_concurrent_driver_never_samples_rows_being_written(masked):
     for s in streams:
         if s is not None:
             s.close()
+
+
+def test_concurrent_driver_refuses_a_lookahead_the_hoisted_step_outruns():
+    """With the hoisted step a row's starts must be cleared two rounds before it is written:
+    an explicit lookahead in [M, 2M) is refused (it was accepted for the plain step, which needs
+    one round), 2M is accepted."""
+    from pytorch_r2d2_amd.engine.concurrent import ConcurrentDriver
+    cfg, rp, eng, actor, _, _ = _concurrent_setup(masked=False, driver=False)
+    assert eng.hoist
+    for D in (4, 6, 7):
+        with pytest.raises(ValueError, match="lookahead"):
+            ConcurrentDriver(eng, actor, steps_per_round=4, lookahead=D)
+    assert not eng.writes_covered and actor.defer is None      # refused before touching either
+    drv = ConcurrentDriver(eng, actor, steps_per_round=4, lookahead=8)
+    assert eng.writes_covered and drv.D == 8
+    drv.run(3)
+    drv.finish()
+    drv.check_errors()
+    assert eng.hoisted_steps == 2
 
 
 def test_run_native_concurrent_and_serial_train():
