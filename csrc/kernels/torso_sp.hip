@@ -776,7 +776,9 @@ extern "C" int r2_torso_fwd_sp_multi(const uint8_t* frames, const int64_t* jobs,
 //       g1 = convT_s2(g2, W2) * (act1 > 0) (4 output phases; W2 phase slices from L2; transposed
 //       product, g1 rows with an 8-byte chunk swizzle that S3's transposed reads undo)
 //   Every [rows][32] image (act1, act2, g3, g2) keeps a 16-byte chunk XOR swizzle (tb_sw).
-//   S2b the frame -> region R as exact bf16 (act1 / act2 are dead by now: R is shared)
+//       the frame -> region R as exact bf16 ahead of the dact1 K loop (R is shared: act1 / act2 are
+//       dead once the dW2 products and the epilogue's mask rows are read); the next frame's load
+//       is issued after the K loop
 //   S3  dW1 += g1 . im2col(frame)         (2 passes: the frame is exact in bf16)
 // dW3 / db3: torso_dw3_sp_kernel.  Slabs and their reduction are shared with the bf16 path.
 namespace tbs {
@@ -799,8 +801,12 @@ constexpr int G1L = G1H + 406 * 32 * 2;
 constexpr int W2ST = G1H, W2PL = 4 * 32 * 128 * 2;        // 32 KB per plane
 constexpr int TBL2 = W2ST + 2 * W2PL;                     // dW2 gather offsets int2 [12][64]
 constexpr int LDS = TBL2 + 12 * 64 * 8;                   // 159232
-// S0 / S1: W3 hi / lo staged in the g1 region (free until S2), rows of W3S bf16
-constexpr int W3S = 296, W3PL = 19 * 1024;                // 32 x 592 B per plane, padded to 19 KB
+// S0 / S1: W3 hi / lo staged in the g1 region (free until S2), rows of W3S bf16.  608-byte rows (38
+// 16-byte chunks, 38 = 6 mod 16): S1's b128 fragment reads (lane = row l16, chunk kg) are served in
+// the lane groups {0-3, 12-15, 20-27}, ..., i.e. 8 rows of one chunk and the other 8 rows of the next
+// chunk, which land on even and odd 16-byte bank groups (37-chunk rows: 2-way conflicts)
+constexpr int W3S = 304, W3PL = 19 * 1024;                // 32 x 608 B per plane = 19 KB
+static_assert(32 * W3S * 2 <= W3PL, "W3 plane");
 constexpr int G2_TRASH = 121, G1_TRASH = 400;
 constexpr int PF1 = (P1 * 4 + NT - 1) / NT;               // act1 chunks per thread per plane (4)
 constexpr int PFF = (IN_CHUNKS + NT - 1) / NT;            // frame chunks per thread (4)
@@ -820,7 +826,7 @@ struct TBSArgs {
   const bf16* w3dg; const bf16* w3dgl;   // (32 ci, 288 = (kh,kw,co)) hi / lo
   const bf16* w2dg; const bf16* w2dgl;   // (4 phases, 32 ci, 128 = (khi,kwi,co)) hi / lo
   float* slab;
-  int n, pad_;
+  int n, dbg;         // dbg: timing-probe bits (r2_torso_bwd_sp_debug), read by the PROBE instance only
   long long* trace;   // optional stage clock stamps of workgroup 0 (r2_torso_bwd_sp_trace)
 };
 
@@ -854,10 +860,14 @@ __device__ __forceinline__ int tb_sw(int r, int e) {
   return r * 32 + ((((e >> 3) ^ (r >> 2)) & 3) << 3) + (e & 7);
 }
 
+// PROBE: the instance the removal probes run (r2_torso_bwd_sp_debug bits != 0: outputs are garbage).
+// The production instance folds dbg to 0, so the probes cost it neither registers nor branches.
+template <bool PROBE>
 __global__ __launch_bounds__(512) void torso_bwd_sp_kernel(const TBSArgs a) {
   using namespace tbs;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int dbg = PROBE ? a.dbg : 0;
 
   // ---- once: zero the bordered gradient images, the dW2 gather table (as torso_bwd.hip)
   for (int i = tid; i < (G1H - G3P) / 16; i += NT) ((u32x4*)(lds + G3P))[i] = u32x4{0, 0, 0, 0};
@@ -916,9 +926,9 @@ __global__ __launch_bounds__(512) void torso_bwd_sp_kernel(const TBSArgs a) {
   __syncthreads();
 
   int it_dbg = 0;
-  long long* tr = (a.trace && blockIdx.x == 0 && lane == 0) ? a.trace + wave * 16 * 11 : nullptr;
+  long long* tr = (a.trace && blockIdx.x == 0 && lane == 0) ? a.trace + wave * 16 * 12 : nullptr;
 #define TBS_STAMP(k) \
-  if (tr && it_dbg < 16) tr[it_dbg * 11 + (k)] = (long long)__builtin_readcyclecounter();
+  if (tr && it_dbg < 16) tr[it_dbg * 12 + (k)] = (long long)__builtin_readcyclecounter();
   for (int f = blockIdx.x; f < a.n; f += gridDim.x) {
     TBS_STAMP(0);
     int oz;
@@ -943,12 +953,12 @@ __global__ __launch_bounds__(512) void torso_bwd_sp_kernel(const TBSArgs a) {
     const bf16* fb1 = fb0 + 4 * 84;
 
     // ======== S0: prefetched activations / gradients -> LDS; W3 hi / lo -> the g1 region by
-    // LDS-DMA (1 KB per wave-instruction, 38 of them: chunk j of a plane = row j / 37, 16-byte
-    // column min(j % 37, 35); the 37th column is the row pad)
-    for (int i = wave; i < 38; i += 8) {
+    // LDS-DMA (1 KB per wave-instruction, 38 of them: chunk j of a plane = row j / 38, 16-byte
+    // column min(j % 38, 35); columns 36 and 37 are the row pad)
+    for (int i = wave; i < ((dbg & 4) && f != (int)blockIdx.x ? 0 : 38); i += 8) {
       const int pl = i >= 19, blk = i - 19 * pl, j = blk * 64 + lane;
-      const int r = j / 37, c = min(j - 37 * r, 35);
-      const bf16* src = (pl ? a.w3dgl : a.w3dg) + (j < 32 * 37 ? r * 288 + c * 8 : 0);
+      const int r = j / 38, c = min(j - 38 * r, 35);
+      const bf16* src = (pl ? a.w3dgl : a.w3dg) + r * 288 + c * 8;
       __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(lds + G1H + pl * W3PL + blk * 1024),
                                        16, 0, 0);
     }
@@ -986,6 +996,7 @@ __global__ __launch_bounds__(512) void torso_bwd_sp_kernel(const TBSArgs a) {
       const bf16* w3h = (const bf16*)(lds + G1H + oz) + l16 * W3S + 8 * kg;
       const bf16* w3l = w3h + W3PL / 2;
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+      if (!(dbg & 8))
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int o = tb_sw(gr - ((t / 3) * 11 + t % 3), 8 * kg);
@@ -1027,7 +1038,7 @@ __global__ __launch_bounds__(512) void torso_bwd_sp_kernel(const TBSArgs a) {
     // dact1 K loop (the dW2 products below run meanwhile).  Chunk j of a plane: phase j / 512,
     // row (j / 16) % 32, 16-byte column (j % 16) ^ (row & 15): the K loop's 32 rows x one column
     // per read hit 16 distinct bank groups
-    for (int i = wave; i < 64; i += 8) {
+    for (int i = wave; i < ((dbg & 1) && f != (int)blockIdx.x ? 0 : 64); i += 8) {
       const int pl = i >> 5, j = (i & 31) * 64 + lane;
       const int ph = j >> 9, r = (j >> 4) & 31, c = (j & 15) ^ (r & 15);
       const bf16* src = (pl ? a.w2dgl : a.w2dg) + (ph * 32 + r) * 128 + c * 8;
@@ -1041,6 +1052,7 @@ __global__ __launch_bounds__(512) void torso_bwd_sp_kernel(const TBSArgs a) {
       const int pb = (nt >> 2) * 20 + (nt & 3);   // act1 pixel of this tile's (kh, kw)
       const int cbl = 16 * ((lane_f >> 4) & 1) + 4 * (lane_f & 3);
       const int2* tl = tbl2 + lane_f;
+      if (!(dbg & 16))
 #pragma unroll
       for (int s = 0; s < 6; ++s) {
         const int x0 = tl[(2 * s) * 64].x, x1 = tl[(2 * s + 1) * 64].x;
@@ -1084,21 +1096,63 @@ __global__ __launch_bounds__(512) void torso_bwd_sp_kernel(const TBSArgs a) {
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's W2 DMAs landed
       __syncthreads();                                     // ... and every other wave's
+      TBS_STAMP(11);
+      // the frame -> R as exact bf16 (the former stage S2b, which had a barrier of its own): act1 /
+      // act2 (R is shared) were last read by the dW2 products and the mask rows above, the K loop
+      // reads g2 and W2 only, and the barrier after the dact1 epilogue orders these stores before S3
+      if (!(dbg & 64)) {
+#pragma unroll
+        for (int k = 0; k < PFF; ++k) {
+          const int c = tid + k * NT;
+          if (c < IN_CHUNKS) {
+            ((bf16x8*)(frb + c * 16))[0] = u8x8_to_bf16(pfr[k][0], pfr[k][1]);
+            ((bf16x8*)(frb + c * 16))[1] = u8x8_to_bf16(pfr[k][2], pfr[k][3]);
+          }
+        }
+      }
       const bf16* w2row = (const bf16*)(lds + W2ST + oz) + (phase * 32 + l32) * 128;
       const int wsw = l32 & 15;
       f32x16 accj[2] = {{}, {}};
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
+      // The operands of step s + 1 are read under the MFMAs of step s, each read KLOOK MFMAs ahead
+      // of the step boundary (sched_group_barrier: 0x100 = LDS read, 0x008 = MFMA).  In source
+      // order every MFMA waited out the LDS round trip of the reads issued just before it; a whole
+      // step ahead (S3's ring) holds both steps' operands at once, which spills here.
+      constexpr int KLOOK = 3;
+      bf16x8 rwh, rwl, rgh[2], rgl[2];
+      auto ldk = [&](int s) {
         const int wo = (((2 * s + half) ^ wsw) << 3);
-        const bf16x8 bh = ts_ld8(w2row + wo), bl = ts_ld8(w2row + W2PL / 2 + wo);
+        rwh = ts_ld8(w2row + wo);
+        rwl = ts_ld8(w2row + W2PL / 2 + wo);
         const int tap = s >> 1;
         const int dr = (tap >> 1) * 11 + (tap & 1), e0 = (s & 1) * 16 + half * 8;
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
           const int o = tb_sw(ab[jj] - dr, e0);
-          accj[jj] = mfma32_x3(bh, bl, ts_ld8(g2p + o), ts_ld8(g2pl + o), accj[jj]);
+          rgh[jj] = ts_ld8(g2p + o);
+          rgl[jj] = ts_ld8(g2pl + o);
+        }
+      };
+      if (!(dbg & 32)) {
+        ldk(0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, KLOOK, 0);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          const bf16x8 bh = rwh, bl = rwl, gh0 = rgh[0], gl0 = rgl[0], gh1 = rgh[1], gl1 = rgl[1];
+          if (s + 1 < 8) ldk(s + 1);
+          accj[0] = mfma32_x3(bh, bl, gh0, gl0, accj[0]);
+          accj[1] = mfma32_x3(bh, bl, gh1, gl1, accj[1]);
+#pragma unroll
+          for (int i = 0; i < 6; ++i) {
+            if (s + 1 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            if (s + 1 < 8 || i + KLOOK < 6) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          }
         }
       }
+      // the next frame's bytes: no vmcnt(0) sits between here and the next S0, which has the
+      // epilogue and the whole of S3 as cover
+      if (f + (int)gridDim.x < a.n && !(dbg & 256)) load_frame(f + gridDim.x);
+      TBS_STAMP(4);
       lds_sync();   // every wave's W2 reads done before g1 (same region) is written
       TBS_STAMP(7);
 #pragma unroll
@@ -1121,31 +1175,20 @@ __global__ __launch_bounds__(512) void torso_bwd_sp_kernel(const TBSArgs a) {
             db1v[4 * g + e] = fmaf(v, keep, db1v[4 * g + e]);
           }
           const int o = row * 32 + (((2 * g + half) ^ sw) << 2);
-          *(bf16x4*)(g1h + o) = vh;
-          *(bf16x4*)(g1l + o) = vl;
+          if (!(dbg & 2)) {
+            *(bf16x4*)(g1h + o) = vh;
+            *(bf16x4*)(g1l + o) = vl;
+          }
         }
       }
     }
-    if (f + (int)gridDim.x < a.n) prefetch_acts(f + gridDim.x);
+    if (f + (int)gridDim.x < a.n && !(dbg & 256)) prefetch_acts(f + gridDim.x);
     TBS_STAMP(8);
-    lds_sync();
+    lds_sync();   // g1 and the frame (stored ahead of the K loop) visible to S3
     TBS_STAMP(3);
 
-    // ======== S2b: frame -> R (act1 / act2 no longer read)
-#pragma unroll
-    for (int k = 0; k < PFF; ++k) {
-      const int c = tid + k * NT;
-      if (c < IN_CHUNKS) {
-        ((bf16x8*)(frb + c * 16))[0] = u8x8_to_bf16(pfr[k][0], pfr[k][1]);
-        ((bf16x8*)(frb + c * 16))[1] = u8x8_to_bf16(pfr[k][2], pfr[k][3]);
-      }
-    }
-    lds_sync();
-    TBS_STAMP(4);
-
     // ======== S3: dW1 += g1 . im2col(frame), 25 K steps of one 4x4 pixel block each (2 passes)
-    if (f + (int)gridDim.x < a.n) load_frame(f + gridDim.x);
-    {
+    if (!(dbg & 128)) {
       constexpr int D = 2;
       bf16x8 rah[D], ral[D], rb[D];
       // g1 rows 16 s + 8 half + q and + 4: their chunk swizzles ((R >> 1) & 7) do not depend on s
@@ -1345,11 +1388,17 @@ extern "C" int r2_torso_grad_reduce(const float* slab, int grid, const int* dst,
                                     float* grad, void* stream);
 
 static long long* g_tbs_trace = nullptr;
-static int g_tbs_dbg = 0;   // timing probes: bit 0 W2 fragments not re-fetched, bit 1 no g1 stores
+// timing probes (removal variants; any bit set runs the PROBE instance and leaves garbage outputs):
+// bit 0 W2 slices staged for the workgroup's first frame only, 1 no g1 stores (dact1 epilogue),
+// 2 W3 staged for the first frame only, 3 no S1 MFMAs, 4 no dW2, 5 no dact1 K loop, 6 no frame
+// conversion, 7 no S3, 8 no next-frame prefetch (activations and frame); any other bit (the probe
+// tool's 0x8000): the PROBE instance with nothing removed
+static int g_tbs_dbg = 0;
 extern "C" int r2_torso_bwd_sp_debug(int bits) { g_tbs_dbg = bits; return 0; }
-// stage clock stamps of workgroup 0: [wave][frame < 16][11] (loop top, after S0, S1, S2, S2b, S3,
-// S2 dW2 part done, S2 dact1 MFMA loop done, S2 epilogue + prefetch issued, S1 tap loop done,
-// S1 epilogue done)
+// stage clock stamps of workgroup 0: [wave][frame < 16][12] (loop top, after S0, S1, S2, dact1 K
+// loop with the frame conversion done + next frame load issued, S3, S2 dW2 part done, the barrier
+// after the K loop passed, S2 epilogue + prefetch issued, S1 tap loop done, S1 epilogue done, the
+// barrier before the dact1 K loop passed)
 extern "C" int r2_torso_bwd_sp_trace(long long* p) { g_tbs_trace = p; return 0; }
 
 // Split-precision torso backward: every activation / gradient operand as hi / lo planes (out3:
@@ -1365,7 +1414,9 @@ extern "C" int r2_torso_bwd_sp(const uint8_t* frames, const int* rows, int n, co
   if (!rows || !act1l || !act2l || !dx3l || !w3dgl || !w2dgl) return -1;
   static bool attr = false;
   if (!attr) {
-    hipFuncSetAttribute((const void*)torso_bwd_sp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipFuncSetAttribute((const void*)torso_bwd_sp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                        tbs::LDS);
+    hipFuncSetAttribute((const void*)torso_bwd_sp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                         tbs::LDS);
     attr = true;
   }
@@ -1373,7 +1424,10 @@ extern "C" int r2_torso_bwd_sp(const uint8_t* frames, const int* rows, int n, co
   TBSArgs a{frames, rows, act1, act1l, act2, act2l, dx3, dx3l, out3, w3dg, w3dgl, w2dg, w2dgl,
             slab, n, g_tbs_dbg, g_tbs_trace};
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(torso_bwd_sp_kernel, dim3(grid), dim3(tbs::NT), tbs::LDS, s, a);
+  if (g_tbs_dbg)
+    hipLaunchKernelGGL(torso_bwd_sp_kernel<true>, dim3(grid), dim3(tbs::NT), tbs::LDS, s, a);
+  else
+    hipLaunchKernelGGL(torso_bwd_sp_kernel<false>, dim3(grid), dim3(tbs::NT), tbs::LDS, s, a);
   hipLaunchKernelGGL(torso_dw3_sp_kernel, dim3(grid), dim3(1024), 0, s, a);
   R2_CHECK_LAUNCH();
   if (!grad) return 0;

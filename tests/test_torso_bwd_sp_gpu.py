@@ -1,0 +1,111 @@
+"""The split-precision torso backward launcher (r2_torso_bwd_sp: torso_bwd_sp_kernel +
+torso_dw3_sp_kernel + the slab reduction) called directly on a few frames, against float64 autograd
+through the same conv stack on the CPU.
+
+Cases: n = 1, 2, 5 frames on 2 workgroups (a workgroup with a single frame, the next-frame
+prefetch edge f + grid < n on both parities, a workgroup that loops three times) and n = 3 on 3.
+Bound (the project's fp32 rule, tests/test_split_gpu.py): each of dW1, dW2, dW3, db1, db2, db3 is
+within 1e-4 of float64, or no worse than 2x what plain fp32 PyTorch's conv backward gives on the same
+inputs.  Every case runs twice: the results must be bit-identical."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda")
+CAP = 8
+NAMES = ["vis_layers.0.weight", "vis_layers.0.bias", "vis_layers.2.weight", "vis_layers.2.bias",
+         "vis_layers.4.weight", "vis_layers.4.bias"]
+
+
+def _rel(a, b):
+    a, b = a.double(), b.double()
+    return ((a - b).norm() / (b.norm() + 1e-300)).item()
+
+
+def _split(x):
+    hi = x.float().to(torch.bfloat16)
+    lo = (x - hi.double()).float().to(torch.bfloat16)
+    return hi.contiguous(), lo.contiguous()
+
+
+def _stack(x, w, dtype):
+    """The conv torso in ``dtype`` on the CPU; returns (act1, act2, out3) as (N, C, H, W)."""
+    x = x.to(dtype) / 255.0
+    a1 = F.relu(F.conv2d(x, w[0].to(dtype), w[1].to(dtype), stride=4))
+    a2 = F.relu(F.conv2d(a1, w[2].to(dtype), w[3].to(dtype), stride=2))
+    o3 = F.relu(F.conv2d(a2, w[4].to(dtype), w[5].to(dtype), stride=1))
+    return a1, a2, o3
+
+
+def _grads(x, w, g, dtype):
+    ws = [p.detach().clone().to(dtype).requires_grad_(True) for p in w]
+    o3 = _stack(x, ws, dtype)[2]
+    (o3.flatten(1) * g.to(dtype)).sum().backward()
+    return [p.grad for p in ws]
+
+
+@pytest.fixture(scope="module")
+def world():
+    """Layout tables, random weights (fp32 values, hi / lo packs) and random uint8 frames."""
+    from pytorch_r2d2_amd.config import get_config
+    from pytorch_r2d2_amd.engine.layout import ParamLayout
+    cfg = get_config("atari57")
+    L = ParamLayout(cfg.model, cfg.env)
+    gen = torch.Generator().manual_seed(1234)
+    flat = torch.zeros(L.padded)
+    for name in NAMES:
+        v = L.view(flat, name)
+        fan = v[0].numel() if v.dim() > 1 else 8
+        v.copy_(torch.randn(v.shape, generator=gen) / fan ** 0.5)
+    idx = L.bf_index.long()
+    hi = flat[idx].to(torch.bfloat16)
+    lo = (flat[idx] - hi.float()).to(torch.bfloat16)
+    pk, pkl = L.packed_views(hi.to(DEV), flat[L.f_index.long()].to(DEV)), \
+        L.packed_views(lo.to(DEV), flat[L.f_index.long()].to(DEV))
+    frames = torch.randint(0, 256, (CAP, 4, 84, 84), dtype=torch.uint8, generator=gen)
+    dst, scale = L.torso_grad_map()
+    return dict(L=L, flat=flat, w=[L.view(flat, n).clone() for n in NAMES], pk=pk, pkl=pkl,
+                frames=frames, frames_dev=frames.view(CAP, -1).to(DEV), dst=dst.to(DEV),
+                scale=scale.to(DEV), gen=gen)
+
+
+@pytest.mark.parametrize("n,grid", [(1, 2), (2, 2), (5, 2), (3, 3)])
+def test_torso_bwd_sp_matches_fp64_autograd(world, n, grid):
+    from pytorch_r2d2_amd.ops._lib import kernels, ptr, stream_handle
+    k = kernels()
+    L, w = world["L"], world["w"]
+    gen = torch.Generator().manual_seed(100 * n + grid)
+    rows = torch.randint(0, CAP, (n,), generator=gen, dtype=torch.int32)
+    x = world["frames"][rows.long()]
+    g = torch.randn(n, 1568, generator=gen)
+    a1, a2, o3 = _stack(x, w, torch.float64)
+    ref = _grads(x, w, g, torch.float64)
+    r32 = _grads(x, w, g, torch.float32)
+
+    a1h, a1l = _split(a1.permute(0, 2, 3, 1).reshape(n, 400, 32))
+    a2h, a2l = _split(a2.permute(0, 2, 3, 1).reshape(n, 81, 32))
+    o3h, _ = _split(o3.flatten(1))
+    dxh, dxl = _split(g.double())
+    dev = [t.to(DEV) for t in (a1h, a1l, a2h, a2l, dxh, dxl, o3h)]
+    rows_d = rows.to(DEV)
+    pk, pkl = world["pk"], world["pkl"]
+    nsl = int(k.r2_torso_bwd_slab_floats())
+    outs = []
+    for _ in range(2):
+        slab = torch.full((grid * nsl,), float("nan"), device=DEV)
+        grad = torch.zeros(L.padded, device=DEV)
+        rc = k.r2_torso_bwd_sp(ptr(world["frames_dev"]), ptr(rows_d), n, *[ptr(t) for t in dev],
+                               ptr(pk["conv3_dg"]), ptr(pkl["conv3_dg"]), ptr(pk["conv2_dg"]),
+                               ptr(pkl["conv2_dg"]), ptr(slab), grid, ptr(world["dst"]),
+                               ptr(world["scale"]), ptr(grad), stream_handle())
+        assert rc == 0
+        torch.cuda.synchronize()
+        outs.append((slab[: min(grid, n) * nsl].cpu(), grad.cpu()))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    assert torch.isfinite(outs[0][0]).all()
+    got = L.views(outs[0][1])
+    errs = {name: (_rel(got[name], r), _rel(r3, r)) for name, r, r3 in zip(NAMES, ref, r32)}
+    print(f"n={n} grid={grid} (kernel, fp32 torch) rel err vs float64: {errs}")
+    bad = {k_: v for k_, v in errs.items() if v[0] > max(1e-4, 2 * v[1])}
+    assert not bad, errs
