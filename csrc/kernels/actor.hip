@@ -29,6 +29,12 @@
 // between its steps (replay.hip apply_pending_kernel).  Rows are invalidated defer_D steps AHEAD
 // of the write head, so by the time a row is overwritten every learner step that could have
 // sampled a sequence through it has finished.
+//
+// Serial clear-ahead (ahead > 0, not deferred; actor.clear_ahead): the same rule applied directly.
+// Every step clears the start `ahead` rows ahead of the write head through clear_row, so the rows
+// head .. head+ahead-1 of every sub-ring never hold a start and a batch the hoisted learner step
+// sampled before the next `ahead` actor steps holds no window they overwrite
+// (LearnerEngine.cover_writes; replay.hip hoist_guard_kernel recounts it on the device).
 #include "../common.h"
 
 struct ActArgs {
@@ -80,6 +86,7 @@ struct ActArgs {
   unsigned long long seed;
   int E, A, H, n, T, stride, cap_e, W, wrap, max_dirty, R, value_rescale;
   int pend_cap, defer_D;      // defer_D > 0: deferred mode, invalidate defer_D rows ahead
+  int ahead;                  // serial mode, ahead > 0: clear the start `ahead` rows ahead instead
   float gamma, gamma_n, prio_eps, alpha, vr_eps;
 };
 
@@ -143,6 +150,12 @@ __global__ __launch_bounds__(256) void actor_pre_kernel(const ActArgs a) {
     // before this step, and a clear queued now would share the pending list with this step's
     // start mark at head-W+1 (the apply kernel runs its entries in no fixed order)
     if (tid == 0) pend_push(a, -2 - (int)(base + (head + a.defer_D) % a.cap_e));
+  } else if (a.ahead > 0) {
+    // serial clear-ahead: rows head .. head+ahead-1 of every sub-ring never hold a start, so a
+    // batch sampled before the next `ahead` steps holds no window those steps overwrite.  No wrap
+    // clears, by the deferred branch's argument: rows cap_e-W+1 .. cap_e-1 were cleared when the
+    // ahead pointer passed them
+    if (tid == 0) clear_row(a, base + (head + a.ahead) % a.cap_e);
   } else {
     if (tid == 0) clear_row(a, row);
     if (a.wrap)
@@ -282,7 +295,8 @@ __global__ void actor_tail_kernel(int64_t* t, int64_t* head, int cap_e, const ui
 
 static bool act_args_ok(const ActArgs& a) {
   return a.E > 0 && a.A > 0 && a.A <= 64 && a.H > 0 && a.n > 0 && a.T > 0 && a.stride > 0 &&
-         a.cap_e > a.W && a.R > 0 && a.FB >= 0 &&
+         a.cap_e > a.W && a.R > 0 && a.FB >= 0 && a.ahead >= 0 && a.cap_e > a.ahead + a.W &&
+         !(a.ahead > 0 && a.defer_D > 0) &&
          (a.defer_D <= 0 || (a.pend && a.pend_cnt && a.pend_cap > 0 && a.cap_e > a.defer_D + a.W));
 }
 

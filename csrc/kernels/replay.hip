@@ -641,6 +641,57 @@ __global__ void step_end_kernel(int64_t* step, int* count) {
   }
 }
 
+// ---- guard of the hoisted learner step under a serial clear-ahead actor (actor.hip ahead > 0;
+// LearnerEngine.cover_writes): the first launch of every step body.  delta = t - t_seen actor steps
+// ran since the previous learner step began, i.e. between the sampling of this step's batch and now;
+// they wrote the min(delta, cap_e) ring offsets ending just before `head` in every sub-ring.  A slot
+// is torn when its learning window [s, s + T) (modular inside its sub-ring) meets them; a bootstrap
+// violation when only [s + T, s + T + n) does and the last learning row is not terminal
+// (engine/replay_check.py check_windows / bootstrap_violations).  A modular window of `len` rows at
+// offset o meets the written run iff, with d = (o - first written offset) mod cap_e, d < c (it
+// starts inside the run) or d + len > cap_e (it wraps round into it).  check: flag the slots
+// (err[0] |= 1, err[1] += slots); the snapshot t_seen = t is refreshed either way.
+__device__ __forceinline__ bool guard_meets(long long o, int len, long long first, long long c,
+                                            int cap_e) {
+  if (c <= 0 || len <= 0) return false;
+  long long d = (o - first) % cap_e;
+  if (d < 0) d += cap_e;
+  return d < c || d + len > cap_e;
+}
+
+__global__ __launch_bounds__(256) void hoist_guard_kernel(
+    const int* __restrict__ starts, int B, const int64_t* __restrict__ head,
+    const int64_t* __restrict__ t, int64_t* __restrict__ t_seen, int cap_e, int n_sub, int T, int n,
+    const uint8_t* __restrict__ done, int check, unsigned* __restrict__ err) {
+  __shared__ int bad;
+  const long long t_now = *t, seen = *t_seen, h = *head;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  if (check) {
+    long long c = t_now - seen;
+    c = c < 0 ? 0 : (c > cap_e ? cap_e : c);
+    const long long first = h - c;        // (guard_meets reduces it mod cap_e)
+    int mine = 0;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+      const long long s = starts[b];
+      if (s < 0 || s >= (long long)n_sub * cap_e) continue;    // never a sampled start
+      const long long base = s - s % cap_e, o = s - base;
+      const bool torn = guard_meets(o, T, first, c, cap_e);
+      const bool ext = guard_meets((o + T) % cap_e, n, first, c, cap_e);
+      mine += torn || (ext && done[base + (o + T - 1) % cap_e] != 1);
+    }
+    if (mine) atomicAdd(&bad, mine);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (bad) {
+      atomicOr(err, 1u);
+      atomicAdd(err + 1, (unsigned)bad);
+    }
+    *t_seen = t_now;
+  }
+}
+
 static TreeGeom make_geom(const int64_t* offs, const int64_t* sizes, int levels) {
   TreeGeom g;
   g.levels = levels;
@@ -929,6 +980,20 @@ extern "C" int r2_gather_state(const float* hs_cs, const int* starts, int B, int
                                int H, bf16* h, float* c, float* h32, void* stream) {
   hipLaunchKernelGGL(gather_state_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, hs_cs,
                      starts, B, off, cap_e, H, h, c, h32);
+  R2_CHECK_LAUNCH();
+  return 0;
+}
+
+// one workgroup, a thread per batch slot (strided past 256); err: 2 words (flag, slot count)
+extern "C" int r2_hoist_guard(const int* starts, int B, const int64_t* head, const int64_t* t,
+                              int64_t* t_seen, int cap_e, int n_sub, int T, int n,
+                              const uint8_t* done, int check, unsigned* err, void* stream) {
+  if (!starts || !head || !t || !t_seen || !done || !err || B <= 0 || cap_e <= 0 || n_sub <= 0 ||
+      T <= 0 || n < 0 || (long long)cap_e * n_sub > 0x7fffffffLL)
+    return -1;
+  hipLaunchKernelGGL(hoist_guard_kernel, dim3(1), dim3(B < 64 ? 64 : (B < 256 ? (B + 63) / 64 * 64 : 256)),
+                     0, (hipStream_t)stream, starts, B, head, t, t_seen, cap_e, n_sub, T, n, done,
+                     check, err);
   R2_CHECK_LAUNCH();
   return 0;
 }

@@ -52,7 +52,7 @@ class ActArgs(ctypes.Structure):
         ("FB", ctypes.c_longlong), ("seed", ctypes.c_ulonglong)] + [
         (name, ctypes.c_int) for name in ("E", "A", "H", "n", "T", "stride", "cap_e", "W", "wrap",
                                           "max_dirty", "R", "value_rescale", "pend_cap",
-                                          "defer_D")] + [
+                                          "defer_D", "ahead")] + [
         (name, ctypes.c_float) for name in ("gamma", "gamma_n", "prio_eps", "alpha", "vr_eps")]
 
 
@@ -171,6 +171,21 @@ class BatchedActor:
         self.defer = None            # dict(pend=[2 x int32], cnt=[2 x int32], cap, D)
         self.lstm_step = False
         self.n_workers = 256         # torso workgroups (grid-stride over frames)
+        # serial clear-ahead (actor.hip, ahead > 0): every step clears the start ``clear_ahead``
+        # rows ahead of the write head instead of the row it overwrites, so a batch the learner
+        # sampled before the next ``clear_ahead`` steps stays whole (LearnerEngine.cover_writes).
+        # It keeps clear_ahead * E starts out of the replay.
+        self.clear_ahead = A_ = int(cfg.actor.clear_ahead)
+        if A_ < 0:
+            raise ValueError("actor.clear_ahead must be >= 0")
+        if A_ > 0:
+            if replay.cap_e <= A_ + W:
+                raise ValueError(f"sub-ring of {replay.cap_e} rows too small for clear_ahead {A_}")
+            # a pre-filled replay starts in the invariant: no start in the first A rows of any ring
+            rows = (self.base[:, None] + (self.head + torch.arange(A_, device=d))[None, :]
+                    % replay.cap_e).reshape(-1)
+            replay.clear_rows(rows)
+            replay.flush_tree()
         if hasattr(env, "reset_all"):
             env.reset_all()
 
@@ -182,6 +197,9 @@ class BatchedActor:
     def enable_deferred(self, pend, cnt, cap: int, lookahead: int) -> None:
         """Deferred (concurrent) mode: ``pend``/``cnt`` = two pending lists + counts (round
         parity); rows are invalidated ``lookahead`` steps ahead of the write head."""
+        if self.clear_ahead > 0:
+            raise ValueError("actor.clear_ahead is the serial loop's rule; the concurrent driver's "
+                             "lookahead does that job (build the actor with clear_ahead=0)")
         if self.replay.cap_e <= lookahead + self.T + self.n:
             raise ValueError(f"sub-ring of {self.replay.cap_e} rows too small for lookahead {lookahead}")
         self.defer = dict(pend=pend, cnt=cnt, cap=int(cap), D=int(lookahead))
@@ -305,6 +323,8 @@ class BatchedActor:
         self.t += 1
         self.head = (self.head + 1) % rp.cap_e
         rp.total_written += self.E
+        if self.clear_ahead > 0:
+            rp.covered_written += self.E
         self.env_steps += self.E
 
     def _args(self, wrap: bool, parity: int = 0) -> ActArgs:
@@ -334,6 +354,7 @@ class BatchedActor:
         if self.defer:
             a.pend, a.pend_cnt = ptr(self.defer["pend"][parity]), ptr(self.defer["cnt"][parity])
             a.pend_cap, a.defer_D = self.defer["cap"], self.defer["D"]
+        a.ahead = self.clear_ahead
         a.gamma, a.gamma_n = self.gamma, self.gamma_n
         a.prio_eps, a.alpha, a.vr_eps = rc.priority_eps, rc.alpha, lc.value_rescale_eps
         return a

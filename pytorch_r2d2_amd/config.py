@@ -195,6 +195,10 @@ class ActorConfig:
     # ablation (tools/learn_check.py): reset both nets' LSTM state before every env step -- a
     # memoryless acting policy (with seq_len 1 and zeroed stored state, a memoryless learner)
     reset_state_every_step: bool = False
+    # serial loop only: clear sequence starts this many rows AHEAD of the write head (actor.hip),
+    # so the hoisted learner step keeps the batch it pre-sampled across up to that many actor
+    # steps (LearnerEngine.cover_writes).  Costs clear_ahead * envs sampleable starts.  0 = off.
+    clear_ahead: int = 0
 
 
 @dataclass

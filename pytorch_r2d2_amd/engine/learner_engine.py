@@ -293,6 +293,7 @@ class LearnerEngine:
         self.hoist = self._hoist_ok()
         self.hoisted_steps = 0        # steps that trained on the batch the previous step sampled
         self.writes_covered = False   # a driver vouches for its replay writes (_hoist_fresh)
+        self._cover = None            # cover_writes: the serial clear-ahead actor's words + guard
         # the sampled batch (starts / probs / rows / stored states) in two sets: the hoisted step
         # k samples step k+1's batch into the other set while its own kernels still read set k % 2
         self._sets = [dict(starts=self.starts, probs=self.probs, rows=self.rows, h0=self.h0, c0=self.c0)]
@@ -443,7 +444,8 @@ class LearnerEngine:
     # replay does not change between the hoisted sample and the step that trains on it.  A batch
     # sampled before a replay write is dropped (_hoist_fresh: HBMReplay.total_written moved), and
     # that step samples at its start like the plain one; only a driver that keeps its writes away
-    # from pending batches (engine/concurrent.py) sets ``writes_covered``.
+    # from pending batches (engine/concurrent.py) sets ``writes_covered``.  ``cover_writes`` keeps
+    # the batch across the steps of a serial actor that clears its starts ahead of its write head.
     def _hoist_ok(self) -> bool:
         lc = self.cfg.learner
         return bool(lc.hoist and self.sp and self.fused_torso and not self.sp_lib
@@ -465,15 +467,75 @@ class LearnerEngine:
         as the plain step does."""
         self._hoist_ready = False
 
+    def cover_writes(self, actor) -> None:
+        """Keep the pre-sampled batch across the steps of ``actor``, a serial ``BatchedActor`` on
+        this engine's replay that clears its starts ``clear_ahead`` rows ahead of its write head
+        (actor.hip, ahead > 0): up to ``clear_ahead`` of its steps between two learner steps
+        overwrite no window of a batch sampled before them (``_hoist_fresh``).  From now on every
+        hoisted step body begins with the device guard (replay.hip hoist_guard_kernel), which
+        recounts that claim from the actor's device step counter and write head and reports torn
+        pre-sampled windows in bit 29 of ``error_word``.  Call before ``capture``."""
+        if getattr(self, "graph", None):
+            raise RuntimeError("cover_writes() must be called before capture(): the guard is a node "
+                               "of every captured step")
+        if actor.replay is not self.replay:
+            raise ValueError("cover_writes: the actor writes another replay")
+        if int(getattr(actor, "clear_ahead", 0)) <= 0:
+            raise ValueError("cover_writes: the actor does not clear ahead (actor.clear_ahead > 0)")
+        if actor.defer:
+            raise ValueError("cover_writes: a deferred actor is covered by the concurrent driver")
+        if not self.hoist:
+            raise ValueError("cover_writes: this engine does not hoist (learner.hoist and its "
+                             "conditions, _hoist_ok)")
+        d = self.device
+        self._cover = dict(actor=actor, head=actor.head_d, t=actor.t_d, A=int(actor.clear_ahead),
+                           t_seen=actor.t_d.clone(),
+                           err=torch.zeros(2, dtype=torch.int32, device=d))
+        self.invalidate_hoist()
+
+    def _guard(self, presampled: bool) -> None:
+        """First operation of a hoisted step body once ``cover_writes`` was called: count the
+        slots of the batch in use whose windows the covered actor's steps since the previous
+        learner step overwrote (only when the batch was ``presampled``), refresh the snapshot."""
+        c = self._cover
+        if c is None:
+            return
+        rp = self.replay
+        check(kernels().r2_hoist_guard(ptr(self.starts), self.B, ptr(c["head"]), ptr(c["t"]),
+                                       ptr(c["t_seen"]), rp.cap_e, rp.n_sub, self.T, self.n,
+                                       ptr(rp.done), int(presampled), ptr(c["err"]), stream_handle()),
+              "hoist_guard")
+
+    def guard_count(self) -> int:
+        """Pre-sampled slots the guard found torn or in bootstrap violation so far (one D2H read;
+        0 without ``cover_writes``)."""
+        return int(self._cover["err"][1].item()) if self._cover is not None else 0
+
+    def _note_presample(self) -> None:
+        """Host state of the moment the next step's batch was sampled (``_hoist_fresh``)."""
+        rp = self.replay
+        self._hoist_gen = rp.total_written
+        if self._cover is not None:
+            self._hoist_unc = rp.total_written - rp.covered_written
+            self._hoist_t = self._cover["actor"].t
+
     def _hoist_fresh(self) -> bool:
         """The previous step sampled this step's batch AND the replay has not been written since
         (every host-side writer bumps ``HBMReplay.total_written``): a batch sampled before a write
         may hold windows the write overwrote, and came from a tree the plain step would not have
         used.  ``writes_covered``: a driver whose writes stay clear of every batch that may
-        still be pending (engine/concurrent.py: lookahead >= 2 rounds) vouches for them."""
-        return bool(getattr(self, "_hoist_ready", False)
-                    and (self.writes_covered
-                         or getattr(self, "_hoist_gen", None) == self.replay.total_written))
+        still be pending (engine/concurrent.py: lookahead >= 2 rounds) vouches for them.
+        ``cover_writes``: no uncovered write (``total_written - covered_written`` has not moved)
+        and at most ``clear_ahead`` steps of the covered actor."""
+        if not getattr(self, "_hoist_ready", False):
+            return False
+        rp = self.replay
+        if self.writes_covered or getattr(self, "_hoist_gen", None) == rp.total_written:
+            return True
+        c = self._cover
+        return bool(c is not None
+                    and getattr(self, "_hoist_unc", None) == rp.total_written - rp.covered_written
+                    and 0 <= c["actor"].t - self._hoist_t <= c["A"])
 
     def _due(self, k: int) -> bool:
         iv = int(self.cfg.learner.target_update_interval)
@@ -566,6 +628,7 @@ class LearnerEngine:
         step: they would use the old target weights)."""
         self._use_set(p)
         self._hoist_due = due
+        self._guard(inm == "H")
         if inm == "P":
             self._sample(qreset=self.tq)
         early = (bool(self.cfg.learner.hoist_early_fork) and self.td_done is not None
@@ -612,7 +675,7 @@ class LearnerEngine:
             self._hoist_body(p, inm, due)
         self.hoisted_steps += inm == "H"
         self._hoist_ready = True
-        self._hoist_gen = self.replay.total_written    # the replay the next batch was sampled from
+        self._note_presample()                         # the replay the next batch was sampled from
         self.steps_done += 1
 
     def _chunk_len(self) -> int:
@@ -638,7 +701,7 @@ class LearnerEngine:
                 self._use_set((m - 1) & 1)
                 self._hoist_due = False
                 self.hoisted_steps += m
-                self._hoist_gen = self.replay.total_written
+                self._note_presample()
                 self.steps_done += m
                 n -= m
             else:
@@ -785,8 +848,9 @@ class LearnerEngine:
                 ptr(pkl["conv3"]), ptr(pk["b3"]), ptr(out), ptr(out_lo)] + s + q
 
     # ------------------------------------------------------------------ the step
-    def _forward_loss(self):
-        self._sample()
+    def _forward_loss(self, _presampled: bool = False):
+        if not _presampled:      # (tests: the caller already ran _sample() for this step)
+            self._sample()
         if self.dp_global:
             self._gather_dp()
         self._forward_rest()
@@ -1477,14 +1541,14 @@ class LearnerEngine:
         self._update()
         self._priorities()
 
-    def _single_body(self, timer=None):
+    def _single_body(self, timer=None, _presampled: bool = False):
         """The world == 1 step as stream operations (eager or captured).  (Running the priority
         refresh + tree repair on a side stream beside the BPTT was measured neutral and removed:
         profiles/r03_prio_side_stream_ab.txt.)"""
         import contextlib
         ph = timer.phase if timer is not None else (lambda name: contextlib.nullcontext())
         with ph("forward+td"):
-            self._forward_loss()
+            self._forward_loss(_presampled)
         with ph("backward_core"):
             self._backward_core()
         with ph("backward_torso"):
@@ -1503,12 +1567,16 @@ class LearnerEngine:
         self._update()
         self.replay.step_end()
 
-    def step_eager(self, timer=None):
+    def step_eager(self, timer=None, _presampled: bool = False):
         """One step without the graph.  ``timer``: optional utils.profiling.PhaseTimer -- every
-        phase is bracketed by HIP events and a roctx range (bench.py --profile-phases)."""
+        phase is bracketed by HIP events and a roctx range (bench.py --profile-phases).
+        ``_presampled`` (private, plain single-rank step only): the caller already sampled this
+        step's batch with ``_sample()``, so the step does not sample at its start."""
         import contextlib
         L = self.layout
         ph = timer.phase if timer is not None else (lambda name: contextlib.nullcontext())
+        if _presampled and (self.hoist or self.dp):
+            raise ValueError("_presampled: the plain single-rank step only")
         if self.hoist:     # (no per-phase timer: the step's phases overlap on two streams)
             g, self.graph = self.graph, None
             try:
@@ -1517,7 +1585,7 @@ class LearnerEngine:
                 self.graph = g
             return
         if not self.dp:
-            self._single_body(timer)
+            self._single_body(timer, _presampled)
             self.steps_done += 1
             return
         with ph("forward+td"):
@@ -1788,16 +1856,25 @@ class LearnerEngine:
     def error_word(self) -> int:
         """The persistent kernels' error word (non-zero: a bounded hand-off spin timed out, so the
         step's recurrent state is garbage; bit 30: the priority tail's grid barrier timed out, so
-        the sum tree missed a repair).  One or two D2H reads."""
+        the sum tree missed a repair; bit 29: the hoist guard of ``cover_writes`` found pre-sampled
+        windows that the covered actor overwrote, so steps trained on torn sequences).  One to
+        three D2H reads."""
         w = int(self.err.item())
         ps = getattr(self.replay, "prio_sync", None)
         if ps is not None and int(ps[3].item()) != 0:
             w |= 1 << 30
+        if self._cover is not None and int(self._cover["err"][0].item()) != 0:
+            w |= 1 << 29      # the hoist guard: a pre-sampled window was overwritten (cover_writes)
         return w
 
     def check_errors(self) -> None:
-        """Raise if a persistent kernel's bounded spin timed out (hand-off failure)."""
+        """Raise if a persistent kernel's bounded spin timed out (hand-off failure), or the hoist
+        guard counted torn pre-sampled windows."""
         w = self.error_word()
+        if w & (1 << 29):
+            raise RuntimeError("hoist guard: %d torn pre-sampled windows (the covered actor wrote rows "
+                               "of batches sampled before its steps; actor.clear_ahead too small "
+                               "for the steps between two learner steps)" % self.guard_count())
         if w & (1 << 30):
             raise RuntimeError("priority tail kernel reported a grid-barrier timeout")
         if w != 0:

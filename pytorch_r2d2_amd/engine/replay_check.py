@@ -90,6 +90,34 @@ def last_learning_row(start: int, cap_e: int, T: int) -> int:
     return base + (start % cap_e + T - 1) % cap_e
 
 
+def _meets_run(off, length: int, first: int, count: int, cap_e: int):
+    """Does the modular window of ``length`` rows at ring offset(s) ``off`` meet the run of
+    ``count`` offsets that begins at ``first``?  With d = (off - first) mod cap_e: it starts inside
+    the run (d < count) or wraps round into it (d + length > cap_e)."""
+    d = (np.asarray(off, dtype=np.int64) - int(first)) % int(cap_e)
+    if count <= 0 or length <= 0:
+        return np.zeros(d.shape, dtype=bool)
+    return (d < count) | (d + int(length) > int(cap_e))
+
+
+def guard_reference(starts, head_now: int, delta: int, cap_e: int, T: int, n: int, done) -> int:
+    """The closed form of the device guard (csrc/kernels/replay.hip hoist_guard_kernel): how many
+    of the sampled global ``starts`` are torn or in bootstrap violation after a writer whose head
+    is now ``head_now`` took ``delta`` steps in every sub-ring, i.e. wrote the
+    ``min(delta, cap_e)`` offsets ending just before ``head_now``.  Equals ``check_windows`` +
+    ``bootstrap_violations`` on ``ring_offsets(head_now - count, count, cap_e)``."""
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    done = np.asarray(done).reshape(-1)
+    cap_e, T, n = int(cap_e), int(T), int(n)
+    count = max(0, min(int(delta), cap_e))
+    first = int(head_now) - count
+    base, off = starts - starts % cap_e, starts % cap_e
+    torn = _meets_run(off, T, first, count, cap_e)
+    ext = _meets_run((off + T) % cap_e, n, first, count, cap_e)
+    last = base + (off + T - 1) % cap_e
+    return int((torn | (ext & (done[last] != 1))).sum())
+
+
 def bootstrap_violations(boot: Sequence[Hit], done, cap_e: int, T: int) -> List[Hit]:
     """The bootstrap overlaps that are NOT allowed: the last learning row is not terminal, so the
     bootstrap would read rows that were being written.  ``done``: the replay's per-row flags."""

@@ -93,6 +93,10 @@ class HBMReplay:
         self.seed = int(cfg.seed) * 0x9E3779B1 + 12345
         self.heads = np.zeros(n_sub, dtype=np.int64)   # per-sub-ring write heads (host mirror)
         self.total_written = 0
+        # rows of ``total_written`` written by an actor that clears its starts ahead of the write
+        # head (BatchedActor.clear_ahead): the writes a covering engine may keep its pre-sampled
+        # batch across (LearnerEngine.cover_writes)
+        self.covered_written = 0
         # trajectory ingest (engine/ingest.py, csrc/kernels/ingest.hip): device-side sub-ring
         # write heads, rows counter and malformed-record flag
         self.ihead = torch.zeros(n_sub, dtype=torch.int64, device=d)

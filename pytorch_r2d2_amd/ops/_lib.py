@@ -62,6 +62,7 @@ _SIGS = {
     "r2_tree_update_fused_reset": [P, P, P, I, P, P, I, P, P],
     "r2_seqprio_refresh": [P, I, P, P, P, I, I, I, I, F, P, P, I, P],
     "r2_mark_starts": [P, P, I, P, P, P, I, I, F, P, P, P, I, P],
+    "r2_hoist_guard": [P, I, P, P, P, I, I, I, I, P, I, P, P],
     "r2_make_rows": [P, I, I, I, I, P, P],
     "r2_sample_batch": [P, P, P, I, I, U64, P, P, P, P, I, I, I, I, P, P, P, P, P],
     "r2_sample_batch_f32h": [P, P, P, I, I, U64, P, P, P, P, I, I, I, I, P, P, P, P, P],

@@ -35,7 +35,10 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
     """``concurrent``: actor group and learner run simultaneously on disjoint CU sets
     (engine/concurrent.py; ``actor_steps_per_update`` env steps per learner step), else they
     alternate on one stream.  ``beat``: supervisor heartbeat; the persistent kernels' error word
-    is checked every ``check_every`` steps (a hand-off timeout stops the run with an error)."""
+    is checked every ``check_every`` steps (a hand-off timeout stops the run with an error).
+    ``cfg.actor.clear_ahead`` > 0 (serial loop only, >= ``actor_steps_per_update``): the actor clears
+    its starts that many rows ahead and the engine keeps its pre-sampled batches across the actor
+    steps (``LearnerEngine.cover_writes``); ``hoisted_steps`` in the result counts them."""
     from .actor_batched import BatchedActor, engine_weights
     from .engine.learner_engine import LearnerEngine
     from .engine.replay_hbm import HBMReplay
@@ -45,6 +48,13 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
     from .utils.faults import Liveness
     from .utils.metrics import MetricsLogger
 
+    ahead = int(cfg.actor.clear_ahead)
+    if ahead > 0 and concurrent:
+        raise ValueError("actor.clear_ahead is the serial loop's rule; the concurrent driver keeps "
+                         "the hoist through its own lookahead")
+    if 0 < ahead < actor_steps_per_update:
+        raise ValueError(f"actor.clear_ahead={ahead} < actor_steps_per_update="
+                         f"{actor_steps_per_update}: every learner step would drop its pre-sampled batch")
     info = init_distributed()
     dev = info.device
     E = cfg.actor.envs_per_actor
@@ -89,6 +99,8 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
     if info.world > 1:
         dist.barrier()
     t_warm = time.perf_counter() - t0
+    if ahead > 0 and eng.hoist:
+        eng.cover_writes(actor)
     if use_graph and cfg.learner.use_graph:
         eng.capture(warmup=1)
     drv = None
@@ -154,6 +166,8 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
            "losses": losses, "returns": list(actor.finished_returns), "env_steps": actor.env_steps,
            "concurrent": bool(concurrent), "learner_cus": eng.n_cus,
            "weights_version": drv.version if drv is not None else None}
+    if eng.hoist:
+        out["hoisted_steps"] = eng.hoisted_steps
     if checkpoint_dir and info.is_main:
         save_full_checkpoint(os.path.join(checkpoint_dir, "full_last.pt"), eng.state_dict(),
                              eng.target_state_dict(), None, eng.steps_done, cfg, eng.full_state_extra())

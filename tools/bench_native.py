@@ -45,6 +45,7 @@ def main():
                "actor_cus_per_xcd": a.actor_cus_per_xcd, "learner_priority": a.learner_priority,
                "learner_steps_per_s": round(out["learner_steps_per_s"], 1),
                "env_steps_per_s": round(out["env_steps_per_s"], 1),
+               "hoisted_steps": out.get("hoisted_steps"), "clear_ahead": cfg.actor.clear_ahead,
                "learner_cus": out["learner_cus"], "dtype": cfg.learner.compute_dtype,
                "batch": cfg.learner.batch_size, "seq_len": cfg.replay.seq_len}
         print(json.dumps(rec), flush=True)
