@@ -41,7 +41,7 @@ struct PTBArgs {
   // recurrence does not use): the dueling head's gradient reduction, (CB x 8) work items
   HeadGradArgs hg;
   int hg_on, hg_wgs;    // hg_wgs: helpers that take head-gradient items (the rest leave at once)
-  // optional stop word (r2_lstm_bwd_set_stop): workgroup (0, 0) stores 0 at iteration 0 and 1 at
+  // optional stop word (BpttOpts::stop): workgroup (0, 0) stores 0 at iteration 0 and 1 at
   // iteration stop_at -- the hoisted target-net torso frames beside this launch (torso_sp.hip
   // qmode 1) stop taking frames then, so they end about when the recurrence does
   unsigned* stop;
@@ -49,7 +49,7 @@ struct PTBArgs {
   // split precision (the _sp launcher): W_hh^T lo plane; dgates lo plane out
   const bf16* whhT_lo;
   bf16* dgates_lo;
-  // split precision, optional (r2_lstm_bwd_set_dz): the dueling head's input gradient dh_ext =
+  // split precision, optional (BpttOpts::dz): the dueling head's input gradient dh_ext =
   // dz . W1 computed HERE instead of read from dh_ext (the TD launch then skips its fused dh, which
   // streamed all of W1^T through every one of its 160 workgroups: 11 us, tools/td_micro.py).  dz
   // (Tl*B, 512) hi / lo planes (time-major learning rows), w1t = W1^T (H, 512) hi / lo planes.
@@ -551,31 +551,17 @@ __global__ __launch_bounds__(320) void lstm_bwd_tag_kernel(const PTBArgs a) {
   }
 }
 
-// in-BPTT dh_ext (PTBArgs::dz): operands for the next r2_lstm_bwd_tag_sp* call on this host
-// thread; dz / w1t hi / lo planes, row length PT_DZ_K.  The launcher copies and clears them on
-// entry, before any check, so a refused call never leaves them armed for a later one.
-static thread_local const bf16* g_bwd_dz[4] = {nullptr, nullptr, nullptr, nullptr};
-extern "C" int r2_lstm_bwd_set_dz(const bf16* dz, const bf16* dz_lo, const bf16* w1t,
-                                  const bf16* w1t_lo, int kd) {
-  if (dz && (!dz_lo || !w1t || !w1t_lo || kd != PT_DZ_K)) return -1;
-  g_bwd_dz[0] = dz; g_bwd_dz[1] = dz_lo; g_bwd_dz[2] = w1t; g_bwd_dz[3] = w1t_lo;
-  return 0;
-}
-// stop word for the next r2_lstm_bwd_tag* call on this host thread (PTBArgs::stop), and the number
-// of helpers that take head-gradient items (0 = all of them); consumed (cleared) on entry like dz
-static thread_local unsigned* g_bwd_stop = nullptr;
-static thread_local int g_bwd_stop_at = 0, g_bwd_hg_wgs = 0;
-extern "C" int r2_lstm_bwd_set_stop(unsigned* stop, int stop_at, int hg_wgs) {
-  if (stop_at < 0 || hg_wgs < 0) return -1;
-  g_bwd_stop = stop;
-  g_bwd_stop_at = stop_at;
-  g_bwd_hg_wgs = hg_wgs;
-  return 0;
-}
-
-// BPTT placement: 1 = recurrence groups packed two per XCD (PTBArgs xcd_map 3), 0 = one per XCD
-static int g_bwd_pairs = 0;
-extern "C" int r2_lstm_bwd_xcd_pairs(int v) { g_bwd_pairs = v; return 0; }
+// Per-launch options of r2_lstm_bwd_tag* (null = none of them).  The launcher copies the fields
+// into PTBArgs during the call and keeps no pointer to the struct.
+struct BpttOpts {
+  // in-BPTT dh_ext (PTBArgs::dz, the _sp launchers at H 256 only): dz / w1t hi / lo planes, row
+  // length kd = PT_DZ_K; dz null = dh_ext is read
+  const bf16 *dz, *dz_lo, *w1t, *w1t_lo;
+  unsigned* stop;   // stop word (PTBArgs::stop), set to 1 at iteration stop_at; null = none
+  int kd, stop_at;
+  int xcd_pairs;    // 1 = recurrence groups packed two per XCD (PTBArgs xcd_map 3), 0 = one per XCD
+};
+extern "C" int r2_lstm_bptt_opts_bytes() { return (int)sizeof(BpttOpts); }
 
 extern "C" int r2_lstm_bwd_tag_ring_bytes(int B, int H) {
   const long long n = 2ll * (H / PL_UNITS) * ((B + PT_ROWS - 1) / PT_ROWS) * PT_ROWS * H * 8;
@@ -602,23 +588,20 @@ static int lstm_bwd_tag_launch(const float* dh_ext, const float* gates, const fl
                                float* db2, const float* hg_dva, const bf16* hg_zr,
                                const float* hg_zr32, const bf16* hg_dz, const bf16* hg_dz_lo,
                                float* hg_gw2, float* hg_gb2, float* hg_gb1, int hg_N, int hg_A,
-                               int hg_HD, float* hg_ws, unsigned* hg_ticket, void* stream) {
-  // host-thread state of this call (set_dz / set_stop), cleared before any check
-  const bf16* dz[4] = {g_bwd_dz[0], g_bwd_dz[1], g_bwd_dz[2], g_bwd_dz[3]};
-  for (int i = 0; i < 4; ++i) g_bwd_dz[i] = nullptr;
-  unsigned* const stop = g_bwd_stop;
-  const int stop_at = g_bwd_stop_at, hg_wgs = g_bwd_hg_wgs;
-  g_bwd_stop = nullptr;
-  g_bwd_stop_at = g_bwd_hg_wgs = 0;
+                               int hg_HD, float* hg_ws, unsigned* hg_ticket, const BpttOpts* opts,
+                               void* stream) {
+  const BpttOpts o = opts ? *opts : BpttOpts{};
+  if (o.dz && (!o.dz_lo || !o.w1t || !o.w1t_lo || o.kd != PT_DZ_K)) return -1;
+  if (o.stop_at < 0) return -1;
   if (B < 1 || T < 1 || t0 < 0 || t0 >= T) return -1;
   if (H != 64 && H != 128 && H != 256 && H != 512) return -2;
   const int MB = (B + PT_ROWS - 1) / PT_ROWS, nwg = H / PL_UNITS;
   if (MB * nwg > g_num_cus || MB > PL_MAX_GROUPS) return -3;
   if ((size_t)T * B * (size_t)(4 * H) * 4 >= (1ull << 32) || r2_lstm_bwd_tag_ring_bytes(B, H) < 0 ||
       T - t0 >= 65535) return -4;
-  // map 3 (r2_lstm_bwd_xcd_pairs): the recurrence packed two groups per XCD, else one per XCD
+  // map 3 (BpttOpts::xcd_pairs): the recurrence packed two groups per XCD, else one per XCD
   int xmap = MB <= 8 && nwg <= 32 && pl_xcd_fit(1, MB, nwg) ? 1 : 0;
-  if (g_bwd_pairs && MB <= 16 && 2 * nwg <= 32 && pl_xcd_fit(3, MB, nwg, true)) xmap = 3;
+  if (o.xcd_pairs && MB <= 16 && 2 * nwg <= 32 && pl_xcd_fit(3, MB, nwg, true)) xmap = 3;
   if (bias_ws && (!perm || !db1)) return -1;
   const bool sp = whhT_lo != nullptr;
   if (sp && (!dgates_lo || H > 256)) return -11;
@@ -627,8 +610,8 @@ static int lstm_bwd_tag_launch(const float* dh_ext, const float* gates, const fl
                HeadGradArgs{hg_dva, hg_zr, hg_dz, hg_gw2, hg_gb2, hg_gb1, hg_ws, hg_ticket, hg_N, hg_A,
                             hg_HD, 8, (hg_A + 6) / 7, hg_zr32, hg_dz_lo},
                0, 0};
-  args.stop = stop;
-  args.stop_at = stop_at;
+  args.stop = o.stop;
+  args.stop_at = o.stop_at;
   args.dbg = g_pl_dbg;
   int taken = 0, nh = 0;
   if (hg_dva) {
@@ -640,7 +623,7 @@ static int lstm_bwd_tag_launch(const float* dh_ext, const float* gates, const fl
       return -5;
     if (sp && (!hg_zr32 || !hg_dz_lo)) return -12;
     args.hg_on = 1;
-    args.hg_wgs = hg_wgs > 0 ? min(hg_wgs, nh) : nh;
+    args.hg_wgs = nh;
     // row splits: one item per head-gradient helper (8 column blocks x NP passes x RS), so the
     // helpers finish early and free their CUs (RS 8 left 64 helpers on 320-row items until ~55 us)
     const int cbn = (2 * hg_HD + 63) / 64;
@@ -649,7 +632,7 @@ static int lstm_bwd_tag_launch(const float* dh_ext, const float* gates, const fl
   }
   args.whhT_lo = whhT_lo;
   args.dgates_lo = dgates_lo;
-  args.dz = dz[0]; args.dz_lo = dz[1]; args.w1t = dz[2]; args.w1t_lo = dz[3];
+  args.dz = o.dz; args.dz_lo = o.dz_lo; args.w1t = o.w1t; args.w1t_lo = o.w1t_lo;
   if (args.dz && (!sp || H != 256)) return -13;   // split-precision T4 BPTT, H 256 only
   // one workgroup per CU (the PL_LDS_RESERVE rule, comment at its definition): the dz path's
   // dynamic LDS (iteration 0's dz rows + the dh partials, 36 KB) plus the kernel's 54 KB of static
@@ -692,11 +675,12 @@ extern "C" int r2_lstm_bwd_tag(const float* dh_ext, const float* gates, const fl
                                float* bias_ws, const int* perm, float* db1, float* db2,
                                const float* hg_dva, const bf16* hg_zr, const bf16* hg_dz,
                                float* hg_gw2, float* hg_gb2, float* hg_gb1, int hg_N, int hg_A,
-                               int hg_HD, float* hg_ws, unsigned* hg_ticket, void* stream) {
+                               int hg_HD, float* hg_ws, unsigned* hg_ticket, const BpttOpts* opts,
+                               void* stream) {
   return lstm_bwd_tag_launch(dh_ext, gates, c_seq, c0, whhT, nullptr, dgates, nullptr, B, T, t0, H,
                              ctr, err, ring, bias_ws, perm, db1, db2, hg_dva, hg_zr, nullptr, hg_dz,
                              nullptr, hg_gw2, hg_gb2, hg_gb1, hg_N, hg_A, hg_HD, hg_ws, hg_ticket,
-                             stream);
+                             opts, stream);
 }
 
 // Split precision: the same launch with W_hh^T given as hi / lo planes and dgates written as hi /
@@ -705,12 +689,13 @@ extern "C" int r2_lstm_bwd_tag_sp(const float* dh_ext, const float* gates, const
                                   const float* c0, const bf16* whhT, const bf16* whhT_lo,
                                   bf16* dgates, bf16* dgates_lo, int B, int T, int t0, int H,
                                   unsigned* ctr, unsigned* err, void* ring, float* bias_ws,
-                                  const int* perm, float* db1, float* db2, void* stream) {
+                                  const int* perm, float* db1, float* db2, const BpttOpts* opts,
+                                  void* stream) {
   if (!whhT_lo || !dgates_lo) return -5;
   return lstm_bwd_tag_launch(dh_ext, gates, c_seq, c0, whhT, whhT_lo, dgates, dgates_lo, B, T, t0, H,
                              ctr, err, ring, bias_ws, perm, db1, db2, nullptr, nullptr, nullptr,
                              nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr,
-                             stream);
+                             opts, stream);
 }
 
 // Split precision with the dueling head's gradient reduction on the launch's idle workgroups
@@ -723,11 +708,12 @@ extern "C" int r2_lstm_bwd_tag_sp_hg(const float* dh_ext, const float* gates, co
                                      const int* perm, float* db1, float* db2, const float* hg_dva,
                                      const float* hg_zr32, const bf16* hg_dz, const bf16* hg_dz_lo,
                                      float* hg_gw2, float* hg_gb2, float* hg_gb1, int hg_N, int hg_A,
-                                     int hg_HD, float* hg_ws, unsigned* hg_ticket, void* stream) {
+                                     int hg_HD, float* hg_ws, unsigned* hg_ticket,
+                                     const BpttOpts* opts, void* stream) {
   if (!whhT_lo || !dgates_lo || !hg_zr32 || !hg_dz_lo) return -5;
   return lstm_bwd_tag_launch(dh_ext, gates, c_seq, c0, whhT, whhT_lo, dgates, dgates_lo, B, T, t0, H,
                              ctr, err, ring, bias_ws, perm, db1, db2, hg_dva, nullptr, hg_zr32, hg_dz,
                              hg_dz_lo, hg_gw2, hg_gb2, hg_gb1, hg_N, hg_A, hg_HD, hg_ws, hg_ticket,
-                             stream);
+                             opts, stream);
 }
 

@@ -864,14 +864,8 @@ extern "C" int r2_seqprio_refresh(const int* starts, int B, const uint8_t* is_st
 // allow the fold (tree_update_fused's conditions) or B > 256 (all workgroups must be resident)
 extern "C" int r2_get_num_cus();   // lstm_persist.hip: CUs of the learner's stream
 
-// TD done flag the NEXT r2_prio_tail_sample launch on this host thread waits for (consumed by it):
-// the hoisted step forks its side branch before the TD launch (td.hip TdDuelArgs::done)
-static thread_local unsigned* g_prio_wait = nullptr;
-extern "C" int r2_prio_tail_set_wait(unsigned* wait) {
-  g_prio_wait = wait;
-  return 0;
-}
-
+// wait (r2_prio_tail_sample, optional): the TD done flag the launch waits for -- the hoisted step
+// forks its side branch before the TD launch (td.hip TdDuelArgs::done)
 static int prio_tail_launch(const int* starts, int B, const uint8_t* is_start, const float* priority,
                             float* tree, const int64_t* offs, const int64_t* sizes, int levels,
                             int T, int upd_lo, int upd_hi, int cap_e, float eta, int* dirty,
@@ -1006,7 +1000,8 @@ extern "C" int r2_step_end(int64_t* step, int* count, void* stream) {
 
 // r2_prio_tail (ending the step: step counter + 1) + the NEXT step's sample (r2_sample_batch_q
 // arguments, the same tree and step counter) in one launch: the hoisted learner step's side
-// branch (engine/learner_engine.py).  sync: 6 zeroed uints.
+// branch (engine/learner_engine.py).  sync: 6 zeroed uints.  wait: null, or the TD done flag the
+// tail waits for on the device (prio_tail_launch).
 extern "C" int r2_prio_tail_sample(const int* starts, int B, const uint8_t* is_start,
                                    const float* priority, float* tree, const int64_t* offs,
                                    const int64_t* sizes, int levels, int T, int upd_lo, int upd_hi,
@@ -1015,9 +1010,7 @@ extern "C" int r2_prio_tail_sample(const int* starts, int B, const uint8_t* is_s
                                    float* s_probs, int* s_rows, int Tn, int H, int nstate,
                                    const int64_t* hs, const int* off, const int64_t* h,
                                    const int64_t* c, int h_f32, unsigned* qreset, int skip_xcds,
-                                   void* stream) {
-  unsigned* const wait = g_prio_wait;   // consumed by this call whatever it returns
-  g_prio_wait = nullptr;
+                                   unsigned* wait, void* stream) {
   if (!step || nstate < 0 || nstate > 3) return -1;
   const SampleBatchArgs sb = make_sample_args(tree, offs, sizes, levels, B, seed, step, s_starts,
                                               s_probs, s_rows, Tn, cap_e, H, nstate, hs, off, h, c,

@@ -216,7 +216,7 @@ struct TdDuelArgs {
   int fuse_fwd;
   // optional stage stamps (r2_td_duel_set_trace): [workgroup][wave][12] s_memrealtime (100 MHz)
   long long* trace;
-  // optional (r2_td_duel_set_done, the hoisted step's early fork): the row priorities go out
+  // optional (r2_td_duel_dh done_flag, the hoisted step's early fork): the row priorities go out
   // write-through and drained before the arrival ticket, and the last arriver stores 1 here --
   // the priority tail launched beside this kernel waits for it (replay.hip prio_tail_kernel)
   unsigned* done;
@@ -604,31 +604,14 @@ extern "C" int r2_td_duel_dh(const float*, const float*, const float*, const int
                              float*, float*, const int*, int, int, int, int, int, float, int, float,
                              float, float, float, float*, unsigned*, const void*, const float*,
                              bf16*, float*, int, bf16*, const float*, const bf16*, const bf16*,
-                             float*, int, void*);
+                             float*, int, const int64_t*, unsigned*, void*);
 
-// Head-forward operands of the fused launch (r2_td_duel_fwd_set, consumed by the next
-// r2_td_duel_dh call on this host thread): 12 int64 {z_on, z_nx, z_tg, b1_on, b1_tg, w2_tg,
-// b2_on, b2_tg, q_on, q_nx, q_tg (q outs may be 0)} -- zr of r2_td_duel_dh becomes an output.
-static thread_local int64_t g_td_fwd[12];
-static thread_local bool g_td_fwd_on = false;
 // Stage-stamp buffer of the next eager launches on this host thread (tools/td_micro.py).  A
 // launch being captured into a graph never takes it (r2_td_duel_dh): the graph would keep
 // writing stamps into the buffer after it is cleared or freed.
 static thread_local long long* g_td_trace = nullptr;
 extern "C" int r2_td_duel_set_trace(long long* tr) {
   g_td_trace = tr;
-  return 0;
-}
-// done flag of the NEXT r2_td_duel_dh launch on this host thread (consumed by it; TdDuelArgs::done)
-static thread_local unsigned* g_td_done = nullptr;
-extern "C" int r2_td_duel_set_done(unsigned* done) {
-  g_td_done = done;
-  return 0;
-}
-extern "C" int r2_td_duel_fwd_set(const int64_t* fwd) {
-  g_td_fwd_on = fwd != nullptr;
-  if (fwd)
-    for (int k = 0; k < 11; ++k) g_td_fwd[k] = fwd[k];
   return 0;
 }
 
@@ -645,11 +628,14 @@ extern "C" int r2_td_duel(const float* q_sa, const float* q_arg, const float* q_
   return r2_td_duel_dh(q_sa, q_arg, q_tgt, starts, probs, action, reward, done, dq, loss, td_abs,
                        priority, is_w, n_valid, Tl, B, A, burn_in, cap_e, gamma_n, value_rescale,
                        vr_eps, alpha, prio_eps, beta, part, ticket, zr, w2, dz, dva, HD, dz_lo, dp,
-                       nullptr, nullptr, nullptr, 0, stream);
+                       nullptr, nullptr, nullptr, 0, nullptr, nullptr, stream);
 }
 
 // + the fused head backward to the LSTM output: dh (Tl*B, H) = dz @ W1 from W1^T (H, 2HD) (and its
 // lo plane in split precision).  H must be 256 (16 waves x 16 columns); w1t = null: not fused.
+// fwd (optional, read during the call): head-forward operands of the fused launch, 11 int64 {z_on,
+// z_nx, z_tg, b1_on, b1_tg, w2_tg, b2_on, b2_tg, q_on, q_nx, q_tg (q outs may be 0)} -- zr then
+// becomes an output.  done_flag (optional): TdDuelArgs::done.
 extern "C" int r2_td_duel_dh(const float* q_sa, const float* q_arg, const float* q_tgt,
                              const int* starts, const float* probs, const uint8_t* action,
                              const float* reward, const uint8_t* done, float* dq, float* loss,
@@ -659,9 +645,7 @@ extern "C" int r2_td_duel_dh(const float* q_sa, const float* q_arg, const float*
                              float beta, float* part, unsigned* ticket, const void* zr,
                              const float* w2, bf16* dz, float* dva, int HD, bf16* dz_lo,
                              const float* dp, const bf16* w1t, const bf16* w1t_lo, float* dh, int H,
-                             void* stream) {
-  unsigned* const td_done = g_td_done;
-  g_td_done = nullptr;
+                             const int64_t* fwd, unsigned* done_flag, void* stream) {
   if (B > 256) return -1;
   if (A < 1 || A > 64) return -3;             // one lane per action
   const int grid = (Tl * B + 15) / 16;
@@ -672,22 +656,21 @@ extern "C" int r2_td_duel_dh(const float* q_sa, const float* q_arg, const float*
                 prio_eps, beta, value_rescale, dp},
                zr, w2, dz, dva, dz_lo, w1t, w1t_lo, dh};
   d.fuse_fwd = 0;
-  d.done = td_done;
-  if (td_done && !priority) return -8;
+  d.done = done_flag;
+  if (done_flag && !priority) return -8;
   {   // never bake a stamp buffer into a captured launch
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     const bool cap = hipStreamIsCapturing((hipStream_t)stream, &st) == hipSuccess &&
                      st != hipStreamCaptureStatusNone;
     d.trace = cap ? nullptr : g_td_trace;
   }
-  if (g_td_fwd_on) {
-    g_td_fwd_on = false;   // one launch per set
+  if (fwd) {
     if (A > HEAD_FWD_MAXA) return -6;
-    for (int k = 0; k < 3; ++k) d.zh[k] = (const void*)g_td_fwd[k];
-    d.b1[0] = (const float*)g_td_fwd[3]; d.b1[1] = (const float*)g_td_fwd[4];
-    d.w2t = (const float*)g_td_fwd[5];
-    d.b2[0] = (const float*)g_td_fwd[6]; d.b2[1] = (const float*)g_td_fwd[7];
-    for (int k = 0; k < 3; ++k) d.qo[k] = (float*)g_td_fwd[8 + k];
+    for (int k = 0; k < 3; ++k) d.zh[k] = (const void*)fwd[k];
+    d.b1[0] = (const float*)fwd[3]; d.b1[1] = (const float*)fwd[4];
+    d.w2t = (const float*)fwd[5];
+    d.b2[0] = (const float*)fwd[6]; d.b2[1] = (const float*)fwd[7];
+    for (int k = 0; k < 3; ++k) d.qo[k] = (float*)fwd[8 + k];
     if (!d.zh[0] || !d.zh[1] || !d.zh[2] || !d.b1[0] || !d.b1[1] || !d.w2t || !d.b2[0] || !d.b2[1])
       return -7;
     d.fuse_fwd = 1;

@@ -49,7 +49,7 @@ import torch
 
 from ..config import R2D2Config
 from ..models.qnet import QNet
-from ..ops._lib import check, kernels, ptr, stream_handle
+from ..ops._lib import bptt_opts, check, kernels, ptr, stream_handle
 from ..ops.gemm import G5_CFGS, Gemm, gemm, gemm_group, gemm_sp, gemm_sp_ws_bytes, group_ws_bytes
 from ..models.qnet import torso_dims
 from ..ops.torso_lib import (fused_torso_fwd_geom, fused_torso_supported, gather_frames_nhwc,
@@ -566,11 +566,10 @@ class LearnerEngine:
             # one launch: the tail ends the step (counter + 1) and samples the next batch from the
             # repaired tree (replay.hip r2_prio_tail_sample); else the separate launches
             S, states = self._sample_dst(nxt)
-            if td_wait:
-                check(kernels().r2_prio_tail_set_wait(ptr(self.td_done)), "prio_tail_set_wait")
             ok = rp.prio_tail_sample(self.starts, B, self.Lb, self.T, S["starts"], S["probs"],
                                      S["rows"], self.Tn, states, self.sp, self.tq,
-                                     skip_xcds=self._bptt_xcds())
+                                     skip_xcds=self._bptt_xcds(),
+                                     td_wait=self.td_done if td_wait else None)
             if not ok and td_wait:
                 # refused on the host (shape / co-residency, e.g. ranks sharing the GPU): the
                 # separate launches cannot wait for TD on the device, so this branch also waits for
@@ -598,13 +597,6 @@ class LearnerEngine:
                 check(kernels().r2_torso_fwd_sp_multi(ptr(rp.frames), arr.ctypes.data, 1, grid,
                                                       stream_handle(side)), "torso_fwd_sp (hoisted)")
         return side
-
-    def _set_bptt_placement(self) -> None:
-        """In front of every tagged BPTT launch, like set_stop / set_dz: the recurrence packed two
-        groups per XCD only beside the hoisted torso frames (alone it runs faster one group per
-        XCD: 100 vs 113 us, profiles/r06_hoist_bptt_placement.txt).  The kernel library keeps one
-        process-wide switch, so each launch sets it from the launching engine's own value."""
-        kernels().r2_lstm_bwd_xcd_pairs(1 if self.hoist else 0)
 
     def _bptt_pairs(self) -> bool:
         """The hoisted BPTT packs its recurrence groups two per XCD (lstm_persist.hip xcd_map 3,
@@ -1050,17 +1042,18 @@ class LearnerEngine:
                 # hoisted step, early fork: the side branch forks here, before the TD launch, and
                 # its priority tail waits on the device for this launch's done flag
                 ef.record(torch.cuda.current_stream(self.device))
-                k.r2_td_duel_set_done(ptr(self.td_done))
+            fwd = 0
             if fuse_fwd:
                 z_on, z_tg, z_nx = self._zs[0], self._zs[1], self._zs[2]
                 self._fwd_arr = np.asarray(
                     [ptr(z_on), ptr(z_nx), ptr(z_tg), ptr(pk["head_b1"]), ptr(pt["head_b1"]),
                      ptr(pt["head_w2"]), ptr(pk["head_b2"]), ptr(pt["head_b2"]), ptr(self.q_on),
                      ptr(self.q_nx), ptr(self.q_tg), 0], dtype=np.int64)
-                k.r2_td_duel_fwd_set(self._fwd_arr.ctypes.data)
+                fwd = self._fwd_arr.ctypes.data
             rc_ = k.r2_td_duel_dh(*targs, ptr(self.zr_on[: Ll * B]), ptr(pk["head_w2"]), ptr(self.dz),
                                   ptr(self.dva), L.HD, ptr(self.dz_lo), dp, w1t, w1t_lo,
-                                  ptr(self.dh) if fuse_dh else 0, L.H, s)
+                                  ptr(self.dh) if fuse_dh else 0, L.H, fwd,
+                                  ptr(self.td_done) if ef is not None else 0, s)
             if ef is not None and rc_ != 0:
                 raise RuntimeError("td_duel refused the early-fork launch (code %d)" % rc_)
             if ef is not None:   # the fallback's fork point (_hoist_side: a refused fused tail)
@@ -1071,7 +1064,6 @@ class LearnerEngine:
                 self._dh_done = fuse_dh or self._dh_in_bptt()
                 return
             if fuse_fwd:   # refused on the host before any launch: separate dueling forward
-                k.r2_td_duel_fwd_set(None)
                 self._duel_fwd(jobs, self._zs)
                 fuse_fwd = False
             if self.sp:
@@ -1117,21 +1109,21 @@ class LearnerEngine:
                 ptr(self.err), ptr(self.ring_b), ptr(self.bias_ws), ptr(self.gate_perm_i32),
                 ptr(L.view(g, "lstm.bias_ih")), ptr(L.view(g, "lstm.bias_hh"))]
         w_jobs, x_job = self._post_bptt_jobs()
-        dz_on = self._dh_in_bptt() and self._duel_done
-        if dz_on:
-            check(k.r2_lstm_bwd_set_dz(ptr(self.dz), ptr(self.dz_lo), ptr(pk["head1T"]),
-                                       ptr(pkl["head1T"]), 2 * HD), "lstm_bwd_set_dz")
         # the hoisted target torso beside this launch stops taking frames hoist_stop_lead
-        # iterations before the recurrence ends; every helper takes head-gradient items
+        # iterations before the recurrence ends; the recurrence packed two groups per XCD only
+        # beside those frames (alone it runs faster one group per XCD: 100 vs 113 us,
+        # profiles/r06_hoist_bptt_placement.txt)
         lc = self.cfg.learner
-        check(k.r2_lstm_bwd_set_stop(ptr(self.tq[2:]) if self.hoist else 0,
-                                     max(0, self.Ll - int(lc.hoist_stop_lead)), 0),
-              "lstm_bwd_set_stop")
-        self._set_bptt_placement()
-        if side_hg:
-            rc = k.r2_lstm_bwd_tag_sp_hg(*bptt, *hg, s)   # >= 0: bit 0 = head grads done here
+        o = dict(stop=ptr(self.tq[2:]) if self.hoist else 0,
+                 stop_at=max(0, self.Ll - int(lc.hoist_stop_lead)),
+                 xcd_pairs=1 if self.hoist else 0)
+        if self._dh_in_bptt() and self._duel_done:
+            o.update(dz=ptr(self.dz), dz_lo=ptr(self.dz_lo), w1t=ptr(pk["head1T"]),
+                     w1t_lo=ptr(pkl["head1T"]), kd=2 * HD)
+        if side_hg:   # rc >= 0: bit 0 = head grads done here
+            rc = k.r2_lstm_bwd_tag_sp_hg(*bptt, *hg, bptt_opts(**o), s)
         else:
-            rc = k.r2_lstm_bwd_tag_sp(*bptt, s)
+            rc = k.r2_lstm_bwd_tag_sp(*bptt, bptt_opts(**o), s)
         check(min(rc, 0), "lstm_bwd_tag_sp")
         if side_hg and not rc & 1:
             check(k.r2_head_grads_sp(*hg, s), "head_grads_sp")
@@ -1311,10 +1303,11 @@ class LearnerEngine:
                     ptr(pk["w_hhT"]), ptr(self.dgates), B, T, Lb, H, ptr(self.ctr), ptr(self.err),
                     ptr(self.ring_b), ptr(self.bias_ws), ptr(self.gate_perm_i32),
                     ptr(L.view(g, "lstm.bias_ih")), ptr(L.view(g, "lstm.bias_hh"))]
-            self._set_bptt_placement()
-            rc = k.r2_lstm_bwd_tag(*base, *self._hg_job, s)
+            # no launch options (opts 0): one recurrence group per XCD -- the hoisted step, which
+            # packs them in pairs, is split precision only (_hoist_ok)
+            rc = k.r2_lstm_bwd_tag(*base, *self._hg_job, 0, s)
             if rc in (-6, -10):   # not enough idle workgroups for the side job: recurrence alone
-                rc = k.r2_lstm_bwd_tag(*base, *([0] * 11), s)
+                rc = k.r2_lstm_bwd_tag(*base, *([0] * 11), 0, s)
             if rc != -3:          # -3: grid too large for one workgroup per CU
                 if rc < 0:
                     check(rc, "lstm_bwd_tag")

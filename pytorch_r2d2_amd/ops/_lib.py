@@ -49,12 +49,12 @@ _SIGS = {
     "r2_td_duel": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, F, F, F, F, P, P,
                    P, P, P, P, I, P, P, P],
     "r2_td_duel_dh": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, F, F, F, F, P, P,
-                      P, P, P, P, I, P, P, P, P, P, I, P],
+                      P, P, P, P, I, P, P, P, P, P, I, P, P, P],
     "r2_dueling_fwd_multi_f32": [P, I, I, I, P],
     "r2_lstm_fwd_tag_sp": [P, I, I, I, I, P, P, P, P],
-    "r2_lstm_bwd_tag_sp": [P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P],
+    "r2_lstm_bwd_tag_sp": [P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P],
     "r2_lstm_bwd_tag_sp_hg": [P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P,
-                              P, P, P, P, P, P, P, I, I, I, P, P, P],
+                              P, P, P, P, P, P, P, I, I, I, P, P, P, P],
     "r2_tree_sample": [P, P, P, I, I, U64, P, P, P, P],
     "r2_tree_rebuild": [P, P, P, I, P],
     "r2_tree_update": [P, P, P, I, P, P, I, P],
@@ -69,8 +69,6 @@ _SIGS = {
     "r2_sample_batch_q": [P, P, P, I, I, U64, P, P, P, P, I, I, I, I, P, P, P, P, I, P, P],
     "r2_torso_fwd_sp_multi": [P, P, I, I, P],
     "r2_torso_sp_debug": [I],
-    "r2_td_duel_set_done": [P],
-    "r2_prio_tail_set_wait": [P],
     "r2_torso_sp_trace": [P],
     "r2_torso_bwd_sp_trace": [P],
     "r2_torso_bwd_sp_debug": [I],
@@ -105,14 +103,11 @@ _SIGS = {
     "r2_torso_fwd_set_debug": [P],
     "r2_lstm_persist_set_debug": [P],
     "r2_lstm_fwd_set_stamps": [P],
-    "r2_td_duel_fwd_set": [P],
     "r2_prio_tail": [P, I, P, P, P, P, P, I, I, I, I, I, F, P, P, I, P, P, I, P],
-    "r2_lstm_bwd_set_dz": [P, P, P, P, I],
-    "r2_lstm_bwd_set_stop": [P, I, I],
-    "r2_lstm_bwd_xcd_pairs": [I],
+    "r2_lstm_bptt_opts_bytes": [],
     "r2_lstm_probes": [],
     "r2_prio_tail_sample": [P, I, P, P, P, P, P, I, I, I, I, I, F, P, P, I, P, P, U64, P, P, P, I,
-                            I, I, P, P, P, P, I, P, I, P],
+                            I, I, P, P, P, P, I, P, I, P, P],
     "r2_prio_tail_pack": [P, I, P, P, P, P, P, I, I, I, I, I, F, P, P, I, P, P, I,
                           P, P, I64, P, P, P, I64, P, P, P, I64, I64, I64, P, P, I64, I64, I64, P],
     "r2_td_duel_set_trace": [P],
@@ -126,7 +121,7 @@ _SIGS = {
     "r2_lstm_fwd_tag": [P, I, I, I, I, P, P, P, P],
     "r2_lstm_tag_ring_bytes": [I, I, I],
     "r2_lstm_bwd_tag": [P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P,
-                        P, P, P, P, P, P, I, I, I, P, P, P],
+                        P, P, P, P, P, P, I, I, I, P, P, P, P],
     "r2_lstm_bwd_tag_hg_ok": [I, I, I],
     "r2_lstm_bwd_tag_ring_bytes": [I, I],
     "r2_lstm_bwd_persist": [P, P, P, P, P, P, P, I, I, I, I, P, P, P],
@@ -207,6 +202,27 @@ class _Strict:
         call.__name__ = name
         self.__dict__[name] = call
         return call
+
+
+class BpttOpts(ctypes.Structure):
+    """Mirror of ``struct BpttOpts`` (csrc/kernels/lstm_bptt.hip): the per-launch options of
+    r2_lstm_bwd_tag*; size checked against the .so by ``bptt_opts``."""
+    _fields_ = [("dz", P), ("dz_lo", P), ("w1t", P), ("w1t_lo", P), ("stop", P),
+                ("kd", I), ("stop_at", I), ("xcd_pairs", I)]
+
+
+_bptt_opts_checked = False
+
+
+def bptt_opts(**fields):
+    """``byref`` of a BpttOpts with the given fields, to pass in the ``opts`` slot (the launcher
+    reads it during the call)."""
+    global _bptt_opts_checked
+    if not _bptt_opts_checked:
+        if ctypes.sizeof(BpttOpts) != kernels().r2_lstm_bptt_opts_bytes():
+            raise RuntimeError("BpttOpts layout differs from csrc/kernels/lstm_bptt.hip")
+        _bptt_opts_checked = True
+    return ctypes.byref(BpttOpts(**fields))
 
 
 def ptr(t) -> int:

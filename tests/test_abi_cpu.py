@@ -31,6 +31,28 @@ def test_ctypes_table_matches_sources():
     assert not [(k, len(v), d[k]) for k, v in _SIGS.items() if d[k] != len(v)]
 
 
+def test_one_shot_setters_are_gone():
+    """Per-launch options are arguments of the launch they belong to (BpttOpts, r2_td_duel_dh
+    fwd / done_flag, r2_prio_tail_sample wait), not values parked by a call made before it.
+    The setters left, in the table and in the sources, are the construction-time process settings
+    and the test / probe switches: no BPTT dz, stop-word or XCD-pairs setter, no TD done-flag or
+    head-forward setter, no priority-tail wait setter."""
+    from pytorch_r2d2_amd.ops._lib import _SIGS
+    kept = re.compile(r"r2_set_(num|xcd)_cus|r2_gemm_set_version|r2_gemm5_set_mode|"
+                      r"r2_\w+_set_(debug|trace|stamps)")
+    names = set(_SIGS) | set(_decls())
+    setters = [n for n in names if re.search(r"_set(_|$)|_xcd_pairs$", n)]
+    assert setters and not [n for n in setters if not kept.fullmatch(n)]
+
+
+def test_bptt_opts_mirror_matches_library():
+    import ctypes
+    from pytorch_r2d2_amd.ops import _lib
+    if not _lib.available():
+        pytest.skip("kernel library not built")
+    assert _lib.kernels().r2_lstm_bptt_opts_bytes() == ctypes.sizeof(_lib.BpttOpts)
+
+
 def test_strict_wrapper_refuses_wrong_arg_count():
     from pytorch_r2d2_amd.ops import _lib
     if not _lib.available():

@@ -143,7 +143,7 @@ def test_lstm_backward_matches_autograd(B, H, impl):
             assert k.r2_lstm_bwd_tag(ptr(dh_ext), ptr(gates), ptr(cseq), ptr(c0), ptr(pk["w_hhT"]),
                                      ptr(dg), B, T, t0, H, ptr(ctr), ptr(err), ptr(ring),
                                      ptr(bias_ws), ptr(perm_i), ptr(db1), ptr(db2), *([0] * 11),
-                                     stream_handle()) == 0
+                                     0, stream_handle()) == 0
         rest = ctr.clone()
         rest[3072 + 32] = rest[3072 + 64] = 0        # the two launch epochs (lstm_persist.hip PT_EPOCH_*)
         assert int(rest.abs().sum().item()) == 0      # counters self-reset by the last workgroup
@@ -623,13 +623,18 @@ def test_fused_prio_tail_sample_matches_tail_then_sample(skip):
     step, then the NEXT batch sampled from the repaired tree inside the same launch, the tail's
     workgroups kept off the first ``skip`` XCD slots) == prio_tail + sample_batch, bit for bit:
     tree, step counter, starts, probabilities, row list, stored states; the frame-queue words are
-    zeroed; every sync word is back to 0."""
+    zeroed; every sync word is back to 0.  A third replay runs the fused launch with ``td_wait``
+    on a word that is already 1 (a word at 0 would spin to the kernel's timeout): the same
+    results, the word cleared, no timeout bit in prio_sync[3]."""
     from pytorch_r2d2_amd.engine.replay_hbm import HBMReplay
     cfg = get_config("atari57", **{"replay.capacity": 64000, "replay.n_subrings": 8})
     a = HBMReplay(cfg, DEV)
     a.fill_synthetic(episode_len=200, seed=3)
     b = HBMReplay(cfg, DEV)
     b.fill_synthetic(episode_len=200, seed=3)
+    c = HBMReplay(cfg, DEV)
+    c.fill_synthetic(episode_len=200, seed=3)
+    word = torch.zeros(1, dtype=torch.int32, device=DEV)
     B, H, Tn = 64, cfg.model.hidden, cfg.replay.seq_len + cfg.replay.n_step
     g = torch.Generator(device=DEV).manual_seed(9)
     z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=DEV)   # noqa: E731
@@ -637,10 +642,11 @@ def test_fused_prio_tail_sample_matches_tail_then_sample(skip):
         idx = z(B, dt=torch.int32)
         a.sample(B, idx, z(B))
         pr = torch.rand(a.capacity, generator=g, device=DEV) * 3
-        for r in (a, b):
+        for r in (a, b, c):
             r.priority.copy_(pr)
         outs = []
-        for r in (a, b):
+        word.fill_(1)
+        for r in (a, b, c):
             st, pb, rows = z(B, dt=torch.int32), z(B), z(Tn * B, dt=torch.int32)
             hs = [(r.hs_cs, 0, z(B, H), z(B, H)), (r.target_hs_cs, 5, z(B, H), z(B, H)),
                   (r.hs_cs, 5, z(B, H), z(B, H))]
@@ -648,18 +654,30 @@ def test_fused_prio_tail_sample_matches_tail_then_sample(skip):
             outs.append((st, pb, rows, hs, q))
             if r is a:
                 assert r.prio_tail_sample(idx, B, 40, 80, st, pb, rows, Tn, hs, True, q, skip_xcds=skip)
+            elif r is c:
+                assert r.prio_tail_sample(idx, B, 40, 80, st, pb, rows, Tn, hs, True, q, skip_xcds=skip,
+                                          td_wait=word)
             else:
                 assert r.prio_tail(idx, B, 40, 80, True)
                 r.sample_batch(B, st, pb, rows, Tn, hs, h_f32=True, qreset=q)
         torch.cuda.synchronize()
         assert torch.equal(a.tree, b.tree) and torch.equal(a.step, b.step)
-        (s0, p0, r0, h0, q0), (s1, p1, r1, h1, q1) = outs
+        (s0, p0, r0, h0, q0), (s1, p1, r1, h1, q1), (s2, p2, r2, h2, q2) = outs
         assert torch.equal(s0, s1) and torch.equal(p0, p1) and torch.equal(r0, r1)
         for (_, _, ha, ca), (_, _, hb, cb) in zip(h0, h1):
             assert torch.equal(ha, hb) and torch.equal(ca, cb)
         assert q0[:2].tolist() == [0, 0] and q0[2:].tolist() == [7, 7]
         assert a.prio_sync.tolist() == [0] * 8, a.prio_sync.tolist()
         assert int(a.dirty_count.item()) == 0
+        # with td_wait: the same batch and tree, the word consumed, no timeout
+        assert torch.equal(c.tree, a.tree) and torch.equal(c.step, a.step)
+        assert torch.equal(s2, s0) and torch.equal(p2, p0) and torch.equal(r2, r0)
+        for (_, _, ha, ca), (_, _, hc, cc) in zip(h0, h2):
+            assert torch.equal(ha, hc) and torch.equal(ca, cc)
+        assert q2.tolist() == q0.tolist()
+        assert int(word.item()) == 0
+        assert c.prio_sync.tolist() == [0] * 8, c.prio_sync.tolist()
+        assert int(c.dirty_count.item()) == 0
 
 
 @pytest.mark.parametrize("N", [2560, 333])
@@ -716,3 +734,163 @@ def test_frames_gather_nhwc_matches_torch(C, H, W, rows):
     ref = src[:, : C * H * W].view(-1, C, H, W).float()
     assert x.shape == ref.shape and x.is_contiguous(memory_format=torch.channels_last)
     assert torch.equal(x.float(), ref)
+
+
+# ---- per-launch options passed as arguments (BpttOpts, r2_td_duel_dh fwd / done_flag): they move
+# work and raise flags only, so every comparison below is bit for bit
+
+
+def _bptt_operands(B, H, T, t0, seed):
+    """Random operands of a tagged BPTT launch.  The launches are compared with each other, not
+    with autograd, so the saved gates need not come from a forward pass."""
+    cfg, net, L, flat, pk = _setup(B, H, seed=seed)
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    Tl, G = T - t0, 4 * H
+    whhT = pk["w_hhT"]
+    return dict(B=B, H=H, T=T, t0=t0, whhT=whhT,
+                whhT_lo=(torch.randn(whhT.shape, generator=g, device=DEV) * 1e-3).bfloat16(),
+                dh=torch.randn(Tl, B, H, generator=g, device=DEV),
+                gates=torch.rand(Tl, B, G, generator=g, device=DEV),
+                cseq=torch.randn(T, B, H, generator=g, device=DEV) * 0.5,
+                c0=torch.randn(B, H, generator=g, device=DEV) * 0.5,
+                perm=L.gate_perm.to(DEV, torch.int32))
+
+
+def _bptt_launch(o, sp, opts):
+    """One tagged BPTT launch on a launch site of its own (zeroed ring + counter block, as the
+    engine allocates them).  Returns (dgates[, dgates_lo], db1, db2)."""
+    k = kernels()
+    B, H, T, t0 = o["B"], o["H"], o["T"], o["t0"]
+    G = 4 * H
+    ctr = torch.zeros(int(k.r2_lstm_persist_ctr_words()), dtype=torch.int32, device=DEV)
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ring = torch.zeros(k.r2_lstm_bwd_tag_ring_bytes(B, H) // 4, dtype=torch.int32, device=DEV)
+    bias_ws = torch.zeros((B + 15) // 16, G, device=DEV)
+    db1 = torch.full((G,), float("nan"), device=DEV)
+    db2 = torch.full((G,), float("nan"), device=DEV)
+    dg = torch.zeros(T - t0, B, G, dtype=torch.bfloat16, device=DEV)
+    dg_lo = torch.zeros_like(dg)
+    tail = (B, T, t0, H, ptr(ctr), ptr(err), ptr(ring), ptr(bias_ws), ptr(o["perm"]), ptr(db1),
+            ptr(db2))
+    head = (ptr(o["dh"]), ptr(o["gates"]), ptr(o["cseq"]), ptr(o["c0"]), ptr(o["whhT"]))
+    if sp:
+        rc = k.r2_lstm_bwd_tag_sp(*head, ptr(o["whhT_lo"]), ptr(dg), ptr(dg_lo), *tail, opts,
+                                  stream_handle())
+    else:
+        rc = k.r2_lstm_bwd_tag(*head, ptr(dg), *tail, *([0] * 11), opts, stream_handle())
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert err.item() == 0
+    return (dg, dg_lo, db1, db2) if sp else (dg, db1, db2)
+
+
+@pytest.mark.parametrize("stop_at,word_after", [(2, 1), (4, 0)])
+def test_bptt_stop_word_is_a_launch_argument(stop_at, word_after):
+    """lstm_bptt.hip BpttOpts::stop on r2_lstm_bwd_tag (B 16, H 64, 4 iterations): workgroup
+    (0, 0) stores 0 at iteration 0 and 1 at iteration ``stop_at`` (4 is never reached); dgates
+    and both bias gradients are those of a launch without options."""
+    from pytorch_r2d2_amd.ops._lib import bptt_opts
+    o = _bptt_operands(16, 64, 6, 2, seed=11)
+    ref = _bptt_launch(o, False, None)
+    word = torch.full((1,), 7, dtype=torch.int32, device=DEV)
+    got = _bptt_launch(o, False, bptt_opts(stop=ptr(word), stop_at=stop_at))
+    assert int(word.item()) == word_after
+    for a, b in zip(got, ref):
+        assert torch.equal(a, b)
+    assert not torch.isnan(ref[1]).any() and torch.equal(ref[1], ref[2])
+
+
+def test_bptt_placement_is_a_launch_argument():
+    """BpttOpts::xcd_pairs on r2_lstm_bwd_tag_sp at B 32, H 256 (two recurrence groups of 16
+    workgroups, the smallest shape xcd_map 3 takes): packed two per XCD, one per XCD, packed
+    again -- a placement that outlived its call would show in the second or third launch; all
+    outputs are equal."""
+    from pytorch_r2d2_amd.ops._lib import bptt_opts
+    o = _bptt_operands(32, 256, 6, 2, seed=12)
+    outs = [_bptt_launch(o, True, bptt_opts(xcd_pairs=v)) for v in (1, 0, 1)]
+    assert not torch.isnan(outs[0][2]).any() and outs[0][0].abs().sum().item() > 0
+    for other in outs[1:]:
+        for a, b in zip(outs[0], other):
+            assert torch.equal(a, b)
+
+
+def _td_duel_case():
+    """The duplicate / overlapping / wrapping starts of test_native_gpu's r2_td_duel case (6 x 8
+    transitions, 6 actions, head width 64, bf16)."""
+    g = torch.Generator(device="cpu").manual_seed(0)
+    Tl, B, A, HD, cap_e = 6, 8, 6, 64, 64
+    n, cap = Tl * B, 2 * cap_e
+    d = lambda t: t.to(DEV).contiguous()  # noqa: E731
+    return dict(
+        n=n, A=A, HD=HD, cap=cap,
+        starts=d(torch.tensor([3, 5, 3, 64 + 10, 60, 7, 5, 62], dtype=torch.int32)),
+        q=[d(torch.randn(n, A, generator=g)) for _ in range(3)],
+        action=d(torch.randint(0, A, (cap,), generator=g).to(torch.uint8)),
+        reward=d(torch.randn(cap, generator=g)), done=d(torch.zeros(cap, dtype=torch.uint8)),
+        zr=d(torch.randn(n, 2 * HD, generator=g).to(torch.bfloat16)),
+        w2=d(torch.randn(1 + A, HD, generator=g)))
+
+
+def _td_duel_dh(c, A=None, priority=True, fwd=None, done_flag=None):
+    """One r2_td_duel_dh launch (no fused dh) into fresh outputs; returns (rc, outputs) with
+    outputs = dq, loss, td_abs, priority, dz, dva after a sync."""
+    k = kernels()
+    n, HD, cap = c["n"], c["HD"], c["cap"]
+    A = c["A"] if A is None else A
+    nan = float("nan")
+    dq = torch.full((n, A), nan, device=DEV)
+    loss, td_abs = torch.full((1,), nan, device=DEV), torch.full((n,), nan, device=DEV)
+    prio = torch.full((cap,), -1.0, device=DEV)
+    dz = torch.full((n, 2 * HD), nan, dtype=torch.bfloat16, device=DEV)
+    dva = torch.full((n, 1 + A), nan, device=DEV)
+    part, ticket = torch.zeros(4096, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+    zr = c["zr"].clone()
+    rc = k.r2_td_duel_dh(ptr(c["q"][0]), ptr(c["q"][1]), ptr(c["q"][2]), ptr(c["starts"]), 0,
+                         ptr(c["action"]), ptr(c["reward"]), ptr(c["done"]), ptr(dq), ptr(loss),
+                         ptr(td_abs), ptr(prio) if priority else 0, 0, 0, 6, 8, A, 2, 64, 0.99, 0,
+                         1e-3, 0.9, 1e-6, 0.0, ptr(part), ptr(ticket), ptr(zr), ptr(c["w2"]), ptr(dz),
+                         ptr(dva), HD, 0, 0, 0, 0, 0, 256,
+                         fwd.ctypes.data if fwd is not None else None, ptr(done_flag),
+                         stream_handle())
+    torch.cuda.synchronize()
+    return rc, (dq, loss, td_abs, prio, dz, dva)
+
+
+def test_td_done_flag_is_a_launch_argument():
+    """td.hip r2_td_duel_dh ``done_flag``: the last arriver raises the word; dq, loss, td_abs,
+    the row priorities, dz and dva are those of the launch without it.  With no priority
+    output the call is refused (-8) before anything is launched."""
+    c = _td_duel_case()
+    rc, ref = _td_duel_dh(c)
+    assert rc == 0 and not any(torch.isnan(t.float()).any() for t in ref)
+    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+    rc, got = _td_duel_dh(c, done_flag=flag)
+    assert rc == 0 and int(flag.item()) != 0
+    for a, b in zip(got, ref):
+        assert torch.equal(a, b)
+    flag.zero_()
+    rc, untouched = _td_duel_dh(c, priority=False, done_flag=flag)
+    assert rc == -8 and int(flag.item()) == 0
+    assert all(torch.isnan(untouched[i].float()).all() for i in (0, 1, 2, 4, 5))
+
+
+def test_td_refused_fused_forward_leaves_nothing_behind():
+    """r2_td_duel_dh with the head-forward operands (``fwd``) and 65 actions is refused (-3);
+    the next plain call, with no disarming call in between, gives the plain outputs and writes
+    no Q rows (a fused forward would)."""
+    c = _td_duel_case()
+    n, A, HD = c["n"], c["A"], c["HD"]
+    rc, ref = _td_duel_dh(c)
+    assert rc == 0
+    z = lambda *s: torch.zeros(s, device=DEV)   # noqa: E731
+    bufs = [z(n, 2 * HD), z(n, 2 * HD), z(n, 2 * HD), z(2 * HD), z(2 * HD), z(1 + A, HD), z(1 + A),
+            z(1 + A), z(n, A), z(n, A), z(n, A)]
+    fwd = np.asarray([ptr(b) for b in bufs] + [0], dtype=np.int64)
+    rc, untouched = _td_duel_dh(c, A=65, fwd=fwd)
+    assert rc == -3
+    assert all(torch.isnan(untouched[i].float()).all() for i in (0, 1, 2, 4, 5))
+    rc, got = _td_duel_dh(c)
+    assert rc == 0
+    for a, b in zip(got, ref):
+        assert torch.equal(a, b)
+    assert all(int(b.abs().sum().item()) == 0 for b in bufs[8:])   # no Q rows written

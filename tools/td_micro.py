@@ -64,15 +64,13 @@ k = kernels()
 
 def launch(fuse_dh, fuse_fwd):
     def f():
-        if fuse_fwd:
-            k.r2_td_duel_fwd_set(fwd.ctypes.data)
         rc = k.r2_td_duel_dh(ptr(q[0]), ptr(q[1]), ptr(q[2]), ptr(starts), ptr(probs), ptr(action),
                              ptr(reward), ptr(done), ptr(dq), ptr(loss), ptr(td_abs), ptr(prio),
                              ptr(is_w), ptr(n_valid), Tl, B, A, Lb, cap, 0.997 ** 5, 1, 1e-3, 0.9,
                              1e-6, 0.6, ptr(part), ptr(ticket), ptr(zr), ptr(w2), ptr(dz), ptr(dva),
                              HD, ptr(dz_lo), 0, ptr(w1t) if fuse_dh else 0,
                              ptr(w1t_lo) if fuse_dh else 0, ptr(dh) if fuse_dh else 0, H,
-                             stream_handle())
+                             fwd.ctypes.data if fuse_fwd else 0, 0, stream_handle())
         assert rc == 0, rc
     return f
 
