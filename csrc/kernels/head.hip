@@ -10,6 +10,7 @@
 // One wave per row; each lane owns 4 of the 256 value-branch and 4 of the 256 advantage-branch
 // features (HD = 256).
 #include "../common.h"
+#include "../head_dot.h"
 #include "../split.h"
 
 #define HEAD_MAXA 32
@@ -64,15 +65,11 @@ __global__ __launch_bounds__(256) void dueling_fwd_kernel(const DuelArgs args) {
       o[HD + lane * PER + e] = (ZT)ha[e];
     }
   }
-  float v = 0.f;
-#pragma unroll
-  for (int e = 0; e < PER; ++e) v += hv[e] * w2[lane * PER + e];
+  float v = head_lane_dot<PER>(hv, w2 + lane * PER);
   v = wave_sum_x(v) + b2[0];
   float amean = 0.f, mine = 0.f;
   for (int a = 0; a < A; ++a) {
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) s += ha[e] * w2[(size_t)(1 + a) * HD + lane * PER + e];
+    float s = head_lane_dot<PER>(ha, w2 + (size_t)(1 + a) * HD + lane * PER);
     s = wave_sum_x(s) + b2[1 + a];
     mine = (a == lane) ? s : mine;
     amean += s;

@@ -16,6 +16,7 @@
 // partials in workgroup order with sc1 loads (MI355X_MICROARCH.md hand-off table, row 1).
 #include <type_traits>
 #include "../common.h"
+#include "../head_dot.h"
 #include "../split.h"
 
 __device__ __forceinline__ float vr_h(float x, float eps) {
@@ -242,18 +243,10 @@ __device__ __forceinline__ float td_duel_row(const ZT (&z)[2 * (HD / 64)], const
     ha[e] = fmaxf((float)z[PER + e] + b1[HD + c], 0.f);
   }
   float part[1 + MAXA];
-  part[0] = 0.f;
+  part[0] = head_lane_dot<PER>(hv, w2 + lane * PER);
 #pragma unroll
-  for (int e = 0; e < PER; ++e) part[0] += hv[e] * w2[lane * PER + e];
-#pragma unroll
-  for (int a = 0; a < MAXA; ++a) {
-    float s = 0.f;
-    if (a < A) {
-#pragma unroll
-      for (int e = 0; e < PER; ++e) s += ha[e] * w2[(1 + a) * HD + lane * PER + e];
-    }
-    part[1 + a] = s;
-  }
+  for (int a = 0; a < MAXA; ++a)
+    part[1 + a] = (a < A) ? head_lane_dot<PER>(ha, w2 + (1 + a) * HD + lane * PER) : 0.f;
   float red[1 + MAXA];
 #pragma unroll
   for (int a = 0; a <= MAXA; ++a) red[a] = (a <= A) ? wave_sum_x(part[a]) : 0.f;
@@ -268,9 +261,7 @@ __device__ __forceinline__ float td_duel_row(const ZT (&z)[2 * (HD / 64)], const
     }
   }
   for (int a = MAXA; a < A; ++a) {
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) s += ha[e] * w2g[(size_t)(1 + a) * HD + lane * PER + e];
+    float s = head_lane_dot<PER>(ha, w2g + (size_t)(1 + a) * HD + lane * PER);
     s = wave_sum_x(s) + b2[1 + a];
     mine = (a == lane) ? s : mine;
     amean += s;
@@ -382,7 +373,9 @@ __global__ __launch_bounds__(1024) void td_duel_kernel(const TdDuelArgs args) {
   float wmax = red[0];
 #pragma unroll
   for (int q = 1; q < NW; ++q) wmax = fmaxf(wmax, red[q]);
-  if (gn) wmax = 1.f;
+  // data-parallel weights are already normalised across ranks.  Every thread needs this, not only
+  // the tid < B that evaluated is_weight (gn): each wave scales its own transition by wst[b] / wmax
+  if (a.dp != nullptr) wmax = 1.f;
   if (tid < a.B && a.is_w && blockIdx.x == 0) a.is_w[tid] = w_t / wmax;
   TD_STAMP(2);
 
