@@ -7,6 +7,9 @@
 // hi (and split-precision lo) planes, at packed position dst4[q] (-1: packed by pack_step's
 // gather); when the target sync is due ((step + 1) % interval == 0, learner.py:107-108) the
 // target master and target packs are written too.
+// The loops are written once over an update functor (opt_pack_items / opt_torso_items): RmsUpd
+// here, AdamUpd (adam_elem.h) for optim.hip's adam_pack_kernel, which reads sq / ga as Adam's
+// first / second moment and alpha as beta1.
 #pragma once
 #include "common.h"
 #include "slab_reduce.h"
@@ -48,13 +51,23 @@ __device__ __forceinline__ float rms_elem(float& sq, float& ga, float p, float g
   return p - lr * gr / (sqrtf(sq - ga * ga) + eps);
 }
 
-__device__ __forceinline__ void rmsprop_pack_items(const RmsPackArgs& a, int64_t first, int64_t stride) {
+// The update as a functor (one pack loop for every optimizer: adam_elem.h AdamUpd is the other):
+// upd(s, m, p, gr) advances the element's two state words and returns the new parameter.
+struct RmsUpd {
+  float lr, alpha, eps;
+  __device__ __forceinline__ float operator()(float& sq, float& ga, float p, float gr) const {
+    return rms_elem(sq, ga, p, gr, lr, alpha, eps);
+  }
+};
+
+template <class Upd>
+__device__ __forceinline__ void opt_pack_items(const RmsPackArgs& a, int64_t first, int64_t stride,
+                                               const Upd upd) {
   float scale = a.gscale;
   if (a.clip_sumsq != nullptr && a.max_norm > 0.f) {
     const float norm = sqrtf(*a.clip_sumsq) * a.gscale;
     if (norm > a.max_norm) scale *= a.max_norm / (norm + 1e-6f);
   }
-  const float lr = a.lr, alpha = a.alpha, eps = a.eps;
   float* __restrict__ p = a.p;
   const float* __restrict__ g = a.g;
   float* __restrict__ sq = a.sq;
@@ -69,7 +82,7 @@ __device__ __forceinline__ void rmsprop_pack_items(const RmsPackArgs& a, int64_t
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float s = sv[e], m = av[e];
-      pv[e] = rms_elem(s, m, pv[e], gv[e] * scale, lr, alpha, eps);
+      pv[e] = upd(s, m, pv[e], gv[e] * scale);
       sv[e] = s;
       av[e] = m;
     }
@@ -96,16 +109,21 @@ __device__ __forceinline__ void rmsprop_pack_items(const RmsPackArgs& a, int64_t
   for (int64_t i = first; i < qend; i += stride) quad(i);
   for (int64_t i = (n4 << 2) + first; i < n && !a.tblocks; i += stride) {
     float sv = sq[i], av = ga[i];
-    p[i] = rms_elem(sv, av, p[i], g[i] * scale, lr, alpha, eps);
+    p[i] = upd(sv, av, p[i], g[i] * scale);
     sq[i] = sv;
     ga[i] = av;
     if (due) a.target[i] = p[i];
   }
 }
 
+__device__ __forceinline__ void rmsprop_pack_items(const RmsPackArgs& a, int64_t first, int64_t stride) {
+  opt_pack_items(a, first, stride, RmsUpd{a.lr, a.alpha, a.eps});
+}
+
 // torso section block blk: column sums of 64 slab columns, then the element update at tdst[e]
 // (the same per-element arithmetic as the quad path; gscale 1 at world 1, no clipping)
-__device__ __forceinline__ void rmsprop_torso_items(const RmsPackArgs& a, int blk) {
+template <class Upd>
+__device__ __forceinline__ void opt_torso_items(const RmsPackArgs& a, int blk, const Upd upd) {
   __shared__ float part[4][64];
   const float s = slab_column_sum(a.slab, a.tG, a.tSL, blk, part);
   const int e = blk * 64 + (int)threadIdx.x;
@@ -114,11 +132,15 @@ __device__ __forceinline__ void rmsprop_torso_items(const RmsPackArgs& a, int bl
   const float gv = s * a.tscale[e];
   a.gw[m] = gv;
   float sv = a.sq[m], av = a.ga[m];
-  const float pv = rms_elem(sv, av, a.p[m], gv * a.gscale, a.lr, a.alpha, a.eps);
+  const float pv = upd(sv, av, a.p[m], gv * a.gscale);
   a.sq[m] = sv;
   a.ga[m] = av;
   a.p[m] = pv;
   if (a.interval <= 1 || ((*a.step) + 1) % a.interval == 0) a.target[m] = pv;
+}
+
+__device__ __forceinline__ void rmsprop_torso_items(const RmsPackArgs& a, int blk) {
+  opt_torso_items(a, blk, RmsUpd{a.lr, a.alpha, a.eps});
 }
 
 // host-side argument checks: 16-B master / grad / state / target, 8-B packs

@@ -79,12 +79,17 @@ class ReplayConfig:
 class LearnerConfig:
     batch_size: int = 8               # learner.py:39
     gamma: float = 0.99               # learner.py:21
-    optimizer: str = "rmsprop_centered"   # learner.py:51 ; or "adam" (paper)
+    # learner.py:51 ; or "adam" (paper).  Both run the fused update + row-pack launch and keep the
+    # hoisted step (optim.hip rmsprop_pack_kernel / adam_pack_kernel)
+    optimizer: str = "rmsprop_centered"
     lr: float = 0.00025 / 4.0
     rms_alpha: float = 0.95
     eps: float = 1.5e-7
     adam_betas: tuple = (0.9, 0.999)
-    grad_clip: float = 0.0            # 0 == off (reference)
+    # global-norm clip, 0 == off (reference).  The norm is one launch with a fixed summation
+    # order (optim.hip r2_grad_sumsq): the same clip scale every run and on every DP rank; the
+    # hoisted step is kept; diagnostics() then reports grad_norm
+    grad_clip: float = 0.0
     value_rescale: bool = False       # h(x) = sign(x)(sqrt(|x|+1)-1)+eps*x  (paper)
     value_rescale_eps: float = 1e-3
     target_update_interval: int = 1000    # learner.py:46
@@ -112,7 +117,9 @@ class LearnerConfig:
     # a gather over the updated master in the pack launch
     fuse_opt_pack: bool = True
     # world 1: the torso backward's slab reduction folded into that optimizer launch (its first
-    # workgroups; optim.hip r2_rmsprop_pack_slab) instead of its own torso_grad_reduce launch
+    # workgroups; optim.hip r2_rmsprop_pack_slab / r2_adam_pack_slab) instead of its own
+    # torso_grad_reduce launch; with grad_clip > 0 it is folded into the norm launch
+    # (r2_grad_sumsq), which needs the torso gradient before the update
     fold_torso_reduce: bool = True
     td_fuse_head_bwd: bool = True     # dueling-head backward inside the TD launch (td_duel_kernel)
     # ... and the heads' dueling FORWARD too (fixed / reference target modes: the TD launch forms

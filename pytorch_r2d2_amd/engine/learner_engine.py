@@ -22,7 +22,8 @@ priority scatters.  Here a step is:
               "torso" beside the priority refresh + tree repair
     update    fused centered RMSprop (or Adam) over the flat master buffer, one pack launch
               producing every bf16 kernel layout, target sync as a device-side
-              `copy_if_due` (graph-safe)
+              `copy_if_due` (graph-safe); with learner.grad_clip one launch before it for the
+              gradient norm, a fixed-order sum (the same bits every run and on every DP rank)
     priority  eta-mix refresh of every overlapping sequence + repair of every dirty sum-tree level
               + the step counter in ONE launch (replay.hip prio_tail_kernel, grid barriers between
               the levels; the 3-launch form when the grid cannot be resident)
@@ -206,15 +207,19 @@ class LearnerEngine:
         self.graph = None
         self.stats: Dict[str, float] = {}
         self._alloc()
-        # world 1 (no gradient all-reduce, no clipping): the torso backward's slab reduction rides
-        # on the optimizer launch (r2_rmsprop_pack_slab: one launch fewer); the torso bucket is the
-        # master's tail, so the update's quad loop stops at its first quad
+        # world 1 (no gradient all-reduce): the torso backward's slab reduction rides on the
+        # optimizer launch (r2_rmsprop_pack_slab / r2_adam_pack_slab: one launch fewer); the torso
+        # bucket is the master's tail, so the update's quad loop stops at its first quad.  With
+        # clipping the norm needs the torso gradient before the update, so the reduction rides on
+        # the norm launch instead (r2_grad_sumsq, ``_fold_in_norm``) and the update is the plain
+        # pack kernel with the clip pointer
         self._fold_tq = None
         if (self.sp and not self.sp_lib and not self.dp and self.world == 1 and lc.fold_torso_reduce
-                and lc.optimizer != "adam" and lc.grad_clip <= 0 and self.row_dst4 is not None
+                and self.row_dst4 is not None
                 and self.fwd_geom is not None and L.torso_offset % 4 == 0
                 and bool((L.row_dst4[L.torso_offset // 4:] < 0).all())):
             self._fold_tq = L.torso_offset // 4
+        self._fold_in_norm = bool(self._fold_tq is not None and lc.grad_clip > 0)
         self._pack(always=True)
         if d.type == "cuda":
             torch.cuda.synchronize(d)
@@ -374,6 +379,10 @@ class LearnerEngine:
         self.gate_perm_i32 = L.gate_perm.to(d, torch.int32)
         self.gs_ws = torch.zeros(int(kernels().r2_gradsum_ws_floats()), dtype=torch.float32, device=d)
         self.gs_ticket = torch.zeros(64, dtype=torch.int32, device=d)
+        # the clip norm's per-workgroup partials and ticket (optim.hip r2_grad_sumsq)
+        if lc.grad_clip > 0:
+            self.gsq_part = z(int(kernels().r2_grad_sumsq_partials()))
+            self.gsq_ticket = z(1, dt=torch.int32)
         # DP global sampling: local shard stats, the all-gathered (W, 3) stats, TD's 4 parameters
         self.dp_send = z(3)
         self.dp_recv = z(max(1, self.world) * 3)
@@ -414,7 +423,8 @@ class LearnerEngine:
 
     def _pack_step(self, interval: int, s, rows_done: bool = False):
         """rows_done: the optimizer already wrote the row packs and the target master
-        (optim.hip rmsprop_pack_kernel): gather only the packs before layout.bf_rows_begin.
+        (optim.hip rmsprop_pack_kernel / adam_pack_kernel): gather only the packs before
+        layout.bf_rows_begin.
         With ``learner.fuse_pack_tail`` on the single-rank step the gather is deferred to the
         priority tail's launch instead (``_priorities``)."""
         if self._fuse_pack_tail() and rows_done:
@@ -446,12 +456,17 @@ class LearnerEngine:
     # that step samples at its start like the plain one; only a driver that keeps its writes away
     # from pending batches (engine/concurrent.py) sets ``writes_covered``.  ``cover_writes`` keeps
     # the batch across the steps of a serial actor that clears its starts ahead of its write head.
+    # Every optimizer setting hoists: the side branch's tail advances the device step counter
+    # before the update runs (the join precedes it), so Adam's step count is the counter itself
+    # there and counter + 1 in the plain step (``_step_off``, the same reason as
+    # ``_baked_interval``); the clip norm (r2_grad_sumsq) is a fixed-order sum, the same bits in
+    # both step shapes.
     def _hoist_ok(self) -> bool:
         lc = self.cfg.learner
         return bool(lc.hoist and self.sp and self.fused_torso and not self.sp_lib
-                    and self.device.type == "cuda" and not self.dp and lc.optimizer != "adam"
+                    and self.device.type == "cuda" and not self.dp
                     and self.row_dst4 is not None and self.cfg.replay.fused_prio_tail
-                    and not lc.zero_stored_state and lc.grad_clip <= 0)
+                    and not lc.zero_stored_state)
 
     def _use_set(self, i: int) -> None:
         self._cur = i
@@ -548,6 +563,12 @@ class LearnerEngine:
         if not self.hoist:
             return int(self.cfg.learner.target_update_interval)
         return 1 if self._hoist_due else 1 << 62
+
+    def _step_off(self) -> int:
+        """Adam's step count is the device step counter + this: 1 in the plain and DP steps (the
+        update runs before the counter advances), 0 in the hoisted step (the side branch's priority
+        tail, joined before the update, already advanced it)."""
+        return 0 if self.hoist else 1
 
     def _side_stream(self):
         if getattr(self, "_side", None) is None:
@@ -1340,7 +1361,8 @@ class LearnerEngine:
     def _backward_torso(self, defer_reduce: bool = False):
         """Conv-torso backward into self.grad.  ``defer_reduce`` (split precision, world 1): the
         per-workgroup gradient slabs are left for the optimizer launch, which sums them
-        (r2_rmsprop_pack_slab); the torso entries of self.grad are written there."""
+        (r2_rmsprop_pack_slab / r2_adam_pack_slab), or with clipping for the norm launch before it
+        (r2_grad_sumsq); the torso entries of self.grad are written there."""
         self._torso_deferred = False
         if self.sp_lib:
             B, Lb, T = self.B, self.Lb, self.T
@@ -1438,15 +1460,42 @@ class LearnerEngine:
         n = L.padded
         gscale = 1.0 / self.world
         clip = 0
+        # the torso backward left its slabs (``_backward_torso(defer_reduce=True)``): the first
+        # launch below that reads the torso gradient sums them
+        slabs = self._fold_tq is not None and getattr(self, "_torso_deferred", False)
+        lo_off = L.bf_numel if self.sp else 0
         if lc.grad_clip > 0:
-            check(k.r2_sumsq(ptr(self.grad), n, ptr(self.clip_buf), s), "sumsq")
+            # fixed-order sum of squares (the same bits every run and on every DP rank), with the
+            # slab reduction on its first workgroups when folded (``_fold_in_norm``)
+            fold = ((ptr(self._tb_slab), self._tb_grid, int(k.r2_torso_bwd_slab_floats()),
+                     ptr(self._tb_dst), ptr(self._tb_scale), ptr(self.grad), self._fold_tq)
+                    if slabs else (0, 0, 0, 0, 0, 0, 0))
+            check(k.r2_grad_sumsq(ptr(self.grad), n, ptr(self.clip_buf), ptr(self.gsq_part),
+                                  ptr(self.gsq_ticket), *fold, s), "grad_sumsq")
             clip = ptr(self.clip_buf)
-        if lc.optimizer == "adam":
+            slabs = False
+        if lc.optimizer == "adam" and self.row_dst4 is None:
             check(k.r2_adam(ptr(self.master), ptr(self.grad), ptr(self.opt_a), ptr(self.opt_b), n,
                             float(lc.lr), float(lc.adam_betas[0]), float(lc.adam_betas[1]),
                             float(lc.eps), gscale, ptr(self.replay.step), clip,
                             float(lc.grad_clip), s), "adam")
-        elif self._fold_tq is not None and getattr(self, "_torso_deferred", False):
+        elif lc.optimizer == "adam":
+            # like the RMSprop branches below: the update writes the row packs and the target
+            # master, the pack launch gathers the rest
+            head = (ptr(self.master), ptr(self.grad), ptr(self.opt_a), ptr(self.opt_b), n,
+                    float(lc.lr), float(lc.adam_betas[0]), float(lc.adam_betas[1]), float(lc.eps),
+                    gscale)
+            tail = (ptr(self.row_dst4), ptr(self.bf), ptr(self.bf_t), lo_off, ptr(self.target),
+                    ptr(self.replay.step), self._baked_interval(), self._step_off())
+            if slabs:
+                check(k.r2_adam_pack_slab(*head, *tail, ptr(self._tb_slab), self._tb_grid,
+                                          int(k.r2_torso_bwd_slab_floats()), ptr(self._tb_dst),
+                                          ptr(self._tb_scale), self._fold_tq, s), "adam_pack_slab")
+            else:
+                check(k.r2_adam_pack(*head, clip, float(lc.grad_clip), *tail, s), "adam_pack")
+            self._pack_step(self._baked_interval(), s, rows_done=True)
+            return
+        elif slabs:
             # + the torso slab reduction (its first workgroups; _backward_torso left the slabs)
             check(k.r2_rmsprop_pack_slab(ptr(self.master), ptr(self.grad), ptr(self.opt_a),
                                          ptr(self.opt_b), n, float(lc.lr), float(lc.rms_alpha),
@@ -1844,6 +1893,9 @@ class LearnerEngine:
                 "is_w_mean", "is_w_min", "priority_sum", "n_valid")
         out = dict(zip(keys, v))
         out["replay_fill"] = rp.size / rp.capacity
+        if self.cfg.learner.grad_clip > 0:
+            # the pre-clip global norm of the (rank-averaged) gradient of the step just taken
+            out["grad_norm"] = float(self.clip_buf.item()) ** 0.5 / self.world
         return out
 
     def error_word(self) -> int:

@@ -81,6 +81,11 @@ _SIGS = {
     "r2_rmsprop_pack_slab": [P, P, P, P, I64, F, F, F, F, P, P, P, I64, P, P, I64, P, I, I, P, P, I64, P],
     "r2_adam": [P, P, P, P, I64, F, F, F, F, F, P, P, F, P],
     "r2_sumsq": [P, I64, P, P],
+    "r2_grad_sumsq": [P, I64, P, P, P, P, I, I, P, P, P, I64, P],
+    "r2_grad_sumsq_partials": [],
+    "r2_adam_pack": [P, P, P, P, I64, F, F, F, F, F, P, F, P, P, P, I64, P, P, I64, I, P],
+    "r2_adam_pack_slab": [P, P, P, P, I64, F, F, F, F, F, P, P, P, I64, P, P, I64, I, P, I, I, P, P,
+                          I64, P],
     "r2_pack_bf16": [P, P, P, I64, P],
     "r2_gather_f32": [P, P, P, I64, P],
     "r2_copy_if_due": [P, P, I64, P, I64, P],
