@@ -136,8 +136,10 @@ struct SampleBatchArgs {
 
 // sequence b of the batch, one 256-thread workgroup (sample_batch_kernel, and prio_tail_kernel's
 // fused sample with COH)
+// pub (COH only): the launch's last sampler, on another XCD, reads every prob afterwards (the DP
+// shard stats): the prob is stored at agent scope
 template <bool COH>
-__device__ __forceinline__ void sample_one(const SampleBatchArgs& a, int b) {
+__device__ __forceinline__ void sample_one(const SampleBatchArgs& a, int b, bool pub = false) {
   __shared__ int s_start;
   const int tid = threadIdx.x;
   if (a.qreset && b == 0 && tid == 0) {
@@ -149,7 +151,8 @@ __device__ __forceinline__ void sample_one(const SampleBatchArgs& a, int b) {
     const int node = tree_descend<COH>(a.tree, a.g, a.B, b, a.seed, a.step, tid, &prob);
     if (tid == 0) {
       a.starts[b] = node;
-      a.probs[b] = prob;
+      if (COH && pub) __hip_atomic_store(a.probs + b, prob, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else a.probs[b] = prob;
       s_start = node;
     }
   }
@@ -361,9 +364,14 @@ __device__ __forceinline__ void prio_grid_barrier(unsigned* ctr, unsigned target
 }
 
 // prio_tail_kernel's fused sample (below): wait for the tree, sample this workgroup's sequences,
-// the last sampler clears the flag words
+// the last sampler clears the flag words.  dp_out (r2_prio_tail_sample_dp, the hoisted DP step): the
+// last sampler also writes the shard stats [root, N, min_b probs[b]] of the batch just sampled, the
+// three floats of dp_stats.hip dp_local_stats_kernel (the same strided min and xor-shuffle order;
+// min is exact in any order).  The probs were stored at agent scope by samplers on other XCDs and
+// drained before their ticket add; they and the root are read with agent-scope loads after an
+// acquire.
 __device__ __forceinline__ void prio_tail_sample(const SampleBatchArgs& sb, unsigned* sync, int nprio,
-                                                 int role) {
+                                                 int role, const int* n_valid, float* dp_out) {
   __shared__ int last_s;
   if (threadIdx.x == 0) {
     unsigned spins = 0;
@@ -376,13 +384,28 @@ __device__ __forceinline__ void prio_tail_sample(const SampleBatchArgs& sb, unsi
     }
   }
   __syncthreads();
-  for (int b = role; b < sb.B; b += nprio) sample_one<true>(sb, b);
+  for (int b = role; b < sb.B; b += nprio) sample_one<true>(sb, b, dp_out != nullptr);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0)
     last_s = __hip_atomic_fetch_add(sync + 5, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
              (unsigned)nprio - 1;
   __syncthreads();
+  if (last_s && dp_out && threadIdx.x < 64) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const int lane = threadIdx.x;
+    float m = 3.402823466e38f;
+    for (int i = lane; i < sb.B; i += 64)
+      m = fminf(m, __hip_atomic_load(sb.probs + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) {
+      dp_out[0] = __hip_atomic_load(sb.tree + sb.g.off[sb.g.levels - 1], __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+      dp_out[1] = (float)*n_valid;
+      dp_out[2] = m;
+    }
+  }
   if (last_s && threadIdx.x == 0) {
     __hip_atomic_store(sync + 4, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(sync + 5, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -408,14 +431,15 @@ __device__ __forceinline__ void prio_tail_sample(const SampleBatchArgs& sb, unsi
 // counter and the top levels write-through, then raises sync[4]; the nprio tail workgroups wait
 // for it and sample sequences b = blockIdx.x, +nprio, ... with agent-scope tree loads (the levels
 // were written by workgroups on other XCDs in this launch); the last of them (ticket sync[5])
-// clears sync[4..5].  sync[3] bit 1: that wait timed out.
+// clears sync[4..5].  sync[3] bit 1: that wait timed out.  With dp_out (r2_prio_tail_sample_dp) that
+// last sampler also writes the sampled batch's DP shard stats (prio_tail_sample above).
 __global__ __launch_bounds__(256) void prio_tail_kernel(
     const int* __restrict__ starts, const uint8_t* __restrict__ is_start,
     const float* __restrict__ priority, float* __restrict__ tree, TreeGeom g, int T, int upd_lo,
     int upd_hi, int cap_e, float eta, int* __restrict__ dirty, int* __restrict__ count,
     int max_dirty, unsigned* __restrict__ sync, int64_t* __restrict__ step, int reset_count,
     int nprio, int npart, int skip, const PackStepArgs pk, const SampleBatchArgs sb,
-    unsigned* __restrict__ wait) {
+    unsigned* __restrict__ wait, const int* __restrict__ n_valid, float* __restrict__ dp_out) {
   __shared__ int last;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   // role of this block among the npart participants.  skip > 0 (the hoisted step): blocks b with
@@ -478,7 +502,7 @@ __global__ __launch_bounds__(256) void prio_tail_kernel(
   __syncthreads();
   const bool sampler = sb.B > 0 && role < nprio;
   if (!last) {
-    if (sampler) prio_tail_sample(sb, sync, nprio, role);
+    if (sampler) prio_tail_sample(sb, sync, nprio, role, n_valid, dp_out);
     return;
   }
   // levels 3.. recomputed by this workgroup alone: level 2 comes from memory (the other
@@ -523,7 +547,7 @@ __global__ __launch_bounds__(256) void prio_tail_kernel(
       __hip_atomic_store(sync + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  if (sampler) prio_tail_sample(sb, sync, nprio, role);
+  if (sampler) prio_tail_sample(sb, sync, nprio, role, n_valid, dp_out);
 }
 
 // ---- mark new sequence starts (actor side): set flag, compute eta-mix, append dirty
@@ -872,7 +896,9 @@ static int prio_tail_launch(const int* starts, int B, const uint8_t* is_start, c
                             int* count, int max_dirty, unsigned* sync, int64_t* step,
                             int reset_count, const PackStepArgs* pk, void* stream,
                             const SampleBatchArgs* sb = nullptr, int skip = 0,
-                            unsigned* wait = nullptr) {
+                            unsigned* wait = nullptr, const int* n_valid = nullptr,
+                            float* dp_out = nullptr) {
+  if (dp_out && (!sb || !n_valid)) return -1;
   if (upd_hi - upd_lo + T - 1 > 2048) return -2;
   if (B <= 0 || B > 256) return -3;
   {   // every workgroup must be resident at once (grid barriers): B <= CUs x blocks per CU
@@ -902,7 +928,8 @@ static int prio_tail_launch(const int* starts, int B, const uint8_t* is_start, c
   if (skip) grid = (npart + 8 - skip - 1) / (8 - skip) * 8;
   hipLaunchKernelGGL(prio_tail_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, starts, is_start,
                      priority, tree, g, T, upd_lo, upd_hi, cap_e, eta, dirty, count, max_dirty, sync,
-                     step, reset_count, B, npart, skip, pk ? *pk : none, sb ? *sb : no_sample, wait);
+                     step, reset_count, B, npart, skip, pk ? *pk : none, sb ? *sb : no_sample, wait,
+                     n_valid, dp_out);
   R2_CHECK_LAUNCH();
   return 0;
 }
@@ -1018,4 +1045,27 @@ extern "C" int r2_prio_tail_sample(const int* starts, int B, const uint8_t* is_s
   return prio_tail_launch(starts, B, is_start, priority, tree, offs, sizes, levels, T, upd_lo, upd_hi,
                           cap_e, eta, dirty, count, max_dirty, sync, step, 1, nullptr, stream, &sb,
                           skip_xcds, wait);
+}
+
+// r2_prio_tail_sample + the DP shard stats of the batch it samples (r2_dp_local_stats: [S_k, N_k,
+// min_b q_k(b)], the same three floats) written by the launch's last sampler workgroup: the hoisted
+// data-parallel step (dist.hoist_dp) publishes the next batch's stats without another graph node
+// on its side branch.  dp_out null: exactly r2_prio_tail_sample.
+extern "C" int r2_prio_tail_sample_dp(const int* starts, int B, const uint8_t* is_start,
+                                      const float* priority, float* tree, const int64_t* offs,
+                                      const int64_t* sizes, int levels, int T, int upd_lo, int upd_hi,
+                                      int cap_e, float eta, int* dirty, int* count, int max_dirty,
+                                      unsigned* sync, int64_t* step, uint64_t seed, int* s_starts,
+                                      float* s_probs, int* s_rows, int Tn, int H, int nstate,
+                                      const int64_t* hs, const int* off, const int64_t* h,
+                                      const int64_t* c, int h_f32, unsigned* qreset, int skip_xcds,
+                                      unsigned* wait, const int* n_valid, float* dp_out,
+                                      void* stream) {
+  if (!step || nstate < 0 || nstate > 3 || (dp_out && !n_valid)) return -1;
+  const SampleBatchArgs sb = make_sample_args(tree, offs, sizes, levels, B, seed, step, s_starts,
+                                              s_probs, s_rows, Tn, cap_e, H, nstate, hs, off, h, c,
+                                              h_f32, qreset);
+  return prio_tail_launch(starts, B, is_start, priority, tree, offs, sizes, levels, T, upd_lo, upd_hi,
+                          cap_e, eta, dirty, count, max_dirty, sync, step, 1, nullptr, stream, &sb,
+                          skip_xcds, wait, dp_out ? n_valid : nullptr, dp_out);
 }

@@ -254,6 +254,15 @@ class DistConfig:
     graph_collectives_multi: bool = True
     one_graph_warm: int = 3
     one_graph_validate: int = 50
+    # the hoisted learner step (learner.hoist) on data-parallel ranks too: step k's priority
+    # tail, step k+1's sample + shard stats (replay.hip r2_prio_tail_sample_dp) and target-torso
+    # frames run on a side stream beside the BPTT; the all-gather stays at the step start and no
+    # collective moves to the side branch, so every rank issues all-gather, core all-reduce,
+    # torso all-reduce whichever variant it replays.  Bit-identical to the serial DP step over
+    # RCCL at one forced rank and over gloo with two ranks on one GPU; no N > 1 RCCL run has
+    # exercised it, hence opt-in (one forced rank: +7.0 .. 7.5 % learner steps/s,
+    # profiles/dp_hoist_force_dp_ab.txt)
+    hoist_dp: bool = False
     learner_steps_per_round: int = 1    # run_split default run length: rounds x this
 
 

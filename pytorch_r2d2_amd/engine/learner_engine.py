@@ -19,7 +19,8 @@ priority scatters.  Here a step is:
               head-gradient reduction on its idle workgroups), weight-gradient + dX GEMMs in
               one grouped launch, fused conv backward from the saved activations
     allreduce (DP) bucket "core" beside the conv backward (which leaves CUs to RCCL), bucket
-              "torso" beside the priority refresh + tree repair
+              "torso" beside the priority refresh + tree repair (with dist.hoist_dp the priority
+              tail instead runs on the hoisted step's side branch beside the BPTT)
     update    fused centered RMSprop (or Adam) over the flat master buffer, one pack launch
               producing every bf16 kernel layout, target sync as a device-side
               `copy_if_due` (graph-safe); with learner.grad_clip one launch before it for the
@@ -108,6 +109,24 @@ def torso_bwd_grid(n_frames: int, reserve_cus: int = 0, n_cus: int = 256) -> int
         return avail
     per = -(-n_frames // avail)
     return -(-n_frames // per)
+
+
+def dp_hoist_plan(dp_global: bool, inm: str):
+    """The hoisted data-parallel step (dist.hoist_dp) as ("segment" | "collective", name) pairs in
+    issue order.  ``inm``: 'P' = the step samples at its start, 'H' = the previous step's side
+    branch sampled.  The collective subsequence depends on neither ``inm`` nor on whether the side
+    branch runs target frames (that is inside "core_side"): ranks decide 'P' / 'H' on their own
+    replay and must still meet at every collective.  The side branch (priority tail, counter, next
+    sample + shard stats, target frames) forks and joins inside "core_side" and holds no collective;
+    there is no priority segment."""
+    if inm not in ("P", "H"):
+        raise ValueError("inm must be 'P' or 'H'")
+    plan = [("segment", "sample")] if inm == "P" else []
+    if dp_global:
+        plan.append(("collective", "all_gather"))        # beside fwd_head, joined before core_side
+    plan += [("segment", "fwd_head"), ("segment", "core_side"), ("collective", "all_reduce_core"),
+             ("segment", "torso"), ("collective", "all_reduce_torso"), ("segment", "update")]
+    return plan
 
 
 class LearnerEngine:
@@ -301,11 +320,16 @@ class LearnerEngine:
         self._cover = None            # cover_writes: the serial clear-ahead actor's words + guard
         # the sampled batch (starts / probs / rows / stored states) in two sets: the hoisted step
         # k samples step k+1's batch into the other set while its own kernels still read set k % 2
-        self._sets = [dict(starts=self.starts, probs=self.probs, rows=self.rows, h0=self.h0, c0=self.c0)]
+        # DP global sampling: the batch's local shard stats belong to its set (the hoisted DP step's
+        # side branch writes the next batch's stats while this step's all-gather has read its own)
+        self.dp_send = z(3)
+        self._sets = [dict(starts=self.starts, probs=self.probs, rows=self.rows, h0=self.h0, c0=self.c0,
+                           dp_send=self.dp_send)]
         if self.hoist:
             self._sets.append(dict(starts=z(B, dt=torch.int32), probs=z(B), rows=z(Tn * B, dt=torch.int32),
                                    h0={k: z(B, H, dt=act_dt) for k in ("on", "tg", "nx")},
-                                   c0={k: z(B, H) for k in ("on", "tg", "nx")}))
+                                   c0={k: z(B, H) for k in ("on", "tg", "nx")},
+                                   dp_send=z(3) if self.dp else self.dp_send))
         self._cur = 0
         Tc = self.Tc
         self.hseq, self.hseq_lo = {}, {}
@@ -383,8 +407,8 @@ class LearnerEngine:
         if lc.grad_clip > 0:
             self.gsq_part = z(int(kernels().r2_grad_sumsq_partials()))
             self.gsq_ticket = z(1, dt=torch.int32)
-        # DP global sampling: local shard stats, the all-gathered (W, 3) stats, TD's 4 parameters
-        self.dp_send = z(3)
+        # DP global sampling: the all-gathered (W, 3) shard stats, TD's 4 parameters (the local
+        # stats, dp_send, are part of the sample set above)
         self.dp_recv = z(max(1, self.world) * 3)
         self.dp_params = z(4)
 
@@ -440,7 +464,8 @@ class LearnerEngine:
                 and self.cfg.replay.fused_prio_tail and not self.hoist)
 
     # ------------------------------------------------------------------ hoisted step
-    # Single-rank split-precision step software-pipelined over two steps (round-6 verdict item
+    # Split-precision step software-pipelined over two steps: single rank, and (opt-in,
+    # dist.hoist_dp: "the hoisted step on data-parallel ranks" below) DP ranks (round-6 verdict item
     # 1; reference: the serial /root/reference/learner.py:68-110).  Step k's priority tail needs
     # only its TD errors and step k+1's sample only the repaired tree, so right after the TD
     # launch a side stream runs [priority tail(k) + step counter, sample(k+1) into the other
@@ -461,10 +486,13 @@ class LearnerEngine:
     # there and counter + 1 in the plain step (``_step_off``, the same reason as
     # ``_baked_interval``); the clip norm (r2_grad_sumsq) is a fixed-order sum, the same bits in
     # both step shapes.
+    # Data-parallel ranks hoist only with dist.hoist_dp (default off: the serial DP step, the same
+    # graphs, kernels and bits as before the knob existed); no N > 1 RCCL run has exercised it.
     def _hoist_ok(self) -> bool:
         lc = self.cfg.learner
         return bool(lc.hoist and self.sp and self.fused_torso and not self.sp_lib
-                    and self.device.type == "cuda" and not self.dp
+                    and self.device.type == "cuda"
+                    and (not self.dp or self.cfg.dist.hoist_dp)
                     and self.row_dst4 is not None and self.cfg.replay.fused_prio_tail
                     and not lc.zero_stored_state)
 
@@ -473,6 +501,7 @@ class LearnerEngine:
         S = self._sets[i]
         self.starts, self.probs, self.rows = S["starts"], S["probs"], S["rows"]
         self.h0, self.c0 = S["h0"], S["c0"]
+        self.dp_send = S["dp_send"]
 
     def invalidate_hoist(self) -> None:
         """Drop the batch the previous step sampled (and the target frames it computed) for the
@@ -590,7 +619,8 @@ class LearnerEngine:
             ok = rp.prio_tail_sample(self.starts, B, self.Lb, self.T, S["starts"], S["probs"],
                                      S["rows"], self.Tn, states, self.sp, self.tq,
                                      skip_xcds=self._bptt_xcds(),
-                                     td_wait=self.td_done if td_wait else None)
+                                     td_wait=self.td_done if td_wait else None,
+                                     **({"dp_out": S["dp_send"]} if self.dp_global else {}))
             if not ok and td_wait:
                 # refused on the host (shape / co-residency, e.g. ranks sharing the GPU): the
                 # separate launches cannot wait for TD on the device, so this branch also waits for
@@ -605,6 +635,7 @@ class LearnerEngine:
                     if not rp.update_tree_and_end_step(True):
                         rp.update_tree()
                         rp.step_end()
+                # (DP global sampling: + r2_dp_local_stats into the next set, on this stream)
                 self._sample(set_idx=nxt, qreset=self.tq)
             if torso:
                 rows = self._sets[nxt]["rows"][self.t_lo_tg * B:]
@@ -644,6 +675,15 @@ class LearnerEngine:
         self._guard(inm == "H")
         if inm == "P":
             self._sample(qreset=self.tq)
+        self._hoist_td_side(due, self._forward_rest)
+        self._seg_torso()
+        self._update()
+
+    def _hoist_td_side(self, due: bool, fwd, before_join=None):
+        """The middle of a hoisted step: ``fwd`` (the forward up to and including the TD launch),
+        the BPTT + post-BPTT group, the side branch forked at the TD launch, and the join.
+        ``before_join`` (the DP step): issued on the main stream after the side branch and before
+        the join -- the core gradient bucket's all-reduce start."""
         early = (bool(self.cfg.learner.hoist_early_fork) and self.td_done is not None
                  and not getattr(self, "_early_refused", False) and not _dispatch_serialized())
         if early:
@@ -652,7 +692,7 @@ class LearnerEngine:
             self._early_fork = torch.cuda.Event()
             self._early_post = None
         try:
-            self._forward_rest()
+            fwd()
         finally:
             after_td, self._early_fork = getattr(self, "_early_fork", None), None
         # (the fork is recorded only by the fused TD + head launch, td_fuse_head_bwd; without it
@@ -670,9 +710,112 @@ class LearnerEngine:
         side = self._hoist_side(torso=not due, after_td=after_td, td_wait=early)
         # join before the conv backward: the side branch ends with the BPTT (joining at the end of
         # the step instead let the side torso slow the conv backward: measured slower)
+        if before_join is not None:
+            before_join()
         main.wait_stream(side)
-        self._seg_torso()
+
+    # ---- the hoisted step on data-parallel ranks (dist.hoist_dp).  The serial DP step runs the
+    # priority tail beside the torso bucket's all-reduce and the counter after the update; here the
+    # tail, the counter, the next sample and its shard stats (replay.hip r2_prio_tail_sample_dp) are
+    # the side branch, so the shard stats become part of the sample set: an 'H' step's all-gather
+    # reads what the previous step's side branch wrote, a 'P' step's what its own sample wrote.
+    # The all-gather stays at the step start beside the forward and no collective runs on the side
+    # branch: whichever variant a rank replays (ranks decide _hoist_fresh on their own replay), it
+    # issues the collectives of ``dp_hoist_plan`` in the same order and meets its peers at each.
+    def _gather_fork(self):
+        """The shard-stats all-gather of the set in use on its own stream, forked from the main
+        stream here (joined by ``_gather_join`` before the heads / TD)."""
+        main = torch.cuda.current_stream(self.device)
+        if getattr(self, "_gather_stream", None) is None:
+            self._gather_stream = torch.cuda.Stream(device=self.device)
+        gs = self._gather_stream
+        gs.wait_stream(main)
+        with torch.cuda.stream(gs):
+            self._gather_dp()
+
+    def _gather_join(self):
+        torch.cuda.current_stream(self.device).wait_stream(self._gather_stream)
+
+    def _hseg_sample(self):            # 'P' only: guard (no pre-sampled batch to check) + sample
+        self._guard(False)
+        self._sample(qreset=self.tq)   # (+ the local shard stats into the set, dp_global)
+
+    def _hseg_fwd_head(self, presampled: bool):
+        if presampled:
+            self._guard(True)
+        self._forward_rest(tail=False)
+
+    def _hseg_core_side(self, due: bool, before_join=None):
+        self._hoist_td_side(due, self._forward_tail, before_join)
+
+    def _hseg_update(self):            # (the side branch's tail already advanced the counter)
         self._update()
+
+    def _hoist_dp_body(self, p: int, inm: str, due: bool):
+        """The hoisted DP step as stream operations (eager, or captured as the one graph with the
+        collectives on their streams).  The segments and collectives of ``dp_hoist_plan`` in its
+        order, except that the core bucket's all-reduce starts before the side branch is joined
+        (inside one capture that is an edge; between segment graphs it cannot be)."""
+        L = self.layout
+        self._use_set(p)
+        self._hoist_due = due
+        if inm == "P":
+            self._hseg_sample()
+        if self.dp_global:
+            self._gather_fork()
+        self._hseg_fwd_head(inm == "H")
+        if self.dp_global:
+            self._gather_join()
+        self._hseg_core_side(due, lambda: self._sync().start(0, L.torso_offset))
+        self._seg_torso()
+        self._sync().start(L.torso_offset, L.padded)
+        self._sync().finish()
+        self._hseg_update()
+
+    def _hoist_dp_segments(self, p: int, inm: str, due: bool):
+        """The hoisted DP step as segment graphs with the collectives issued by the host between
+        them (gloo; the dist.one_graph_warm steps; after a rollout fallback), driven by
+        ``dp_hoist_plan``."""
+        L = self.layout
+        self._use_set(p)
+        self._hoist_due = due
+        key = {"sample": (p,), "fwd_head": (p, inm), "core_side": (p, due), "torso": (p,),
+               "update": (due,)}
+        coll = {"all_gather": self._gather_fork,
+                "all_reduce_core": lambda: self._sync().start(0, L.torso_offset),
+                "all_reduce_torso": lambda: (self._sync().start(L.torso_offset, L.padded),
+                                             self._sync().finish())}
+        for kind, name in dp_hoist_plan(self.dp_global, inm):
+            if kind == "collective":
+                coll[name]()
+                continue
+            if name == "core_side" and self.dp_global:
+                self._gather_join()
+            self._hsegs[(name,) + key[name]].replay()
+
+    def _capture_hoist_dp(self):
+        """Every segment graph ``_hoist_dp_segments`` can ask for: sample (set), forward up to the
+        heads (set x 'P' / 'H': the guard checks a pre-sampled batch), heads + TD + BPTT + side
+        branch + join (set x due), torso backward (set), update (due)."""
+        self._hsegs, pool = {}, None
+        cur, due0 = self._cur, getattr(self, "_hoist_due", False)
+        todo = [(("sample", p), self._hseg_sample, ()) for p in (0, 1)]
+        todo += [(("fwd_head", p, i), self._hseg_fwd_head, (i == "H",)) for p in (0, 1) for i in "PH"]
+        todo += [(("core_side", p, d), self._hseg_core_side, (d,)) for p in (0, 1) for d in (False, True)]
+        todo += [(("torso", p), self._seg_torso, ()) for p in (0, 1)]
+        todo += [(("update", d), self._hseg_update, ()) for d in (False, True)]
+        for key, fn, args in todo:
+            if key[0] != "update":
+                self._use_set(key[1])
+            self._hoist_due = bool(key[-1]) if key[0] in ("core_side", "update") else False
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=pool, capture_error_mode=self._capture_mode()):
+                fn(*args)
+            pool = g.pool()
+            self._hsegs[key] = g
+            self.graphs.append(g)
+        self._use_set(cur)
+        self._hoist_due = due0
 
     def _hoist_step(self):
         k = self.steps_done
@@ -681,7 +824,16 @@ class LearnerEngine:
         due = self._due(k + self._dev_step_off)
         p = k & 1
         inm = "H" if self._hoist_fresh() else "P"
-        if self.graph:
+        if self.dp:
+            if not self.graph:
+                self._hoist_dp_body(p, inm, due)
+            elif self._rollout.mode == "one":
+                self._use_set(p)
+                self._hoist_due = due
+                self._one_graphs[(p, inm, due)].replay()
+            else:
+                self._hoist_dp_segments(p, inm, due)
+        elif self.graph:
             self._use_set(p)
             self._hgraphs[(p, inm, due)].replay()
         else:
@@ -690,9 +842,13 @@ class LearnerEngine:
         self._hoist_ready = True
         self._note_presample()                         # the replay the next batch was sampled from
         self.steps_done += 1
+        if self.dp and self.graph:
+            self._dp_rollout_after_step()
 
     def _chunk_len(self) -> int:
-        return max(1, int(getattr(self.cfg.learner, "graph_chunk", 1))) if self.hoist else 1
+        if not self.hoist or self.dp:     # (no multi-step chunk graph at DP: run_steps -> step)
+            return 1
+        return max(1, int(getattr(self.cfg.learner, "graph_chunk", 1)))
 
     def run_steps(self, n: int) -> None:
         """``n`` learner steps, the same work and results as ``n`` calls of ``step``.  In the
@@ -887,11 +1043,11 @@ class LearnerEngine:
         if self.dp_global:
             root = rp.tree[int(rp.tree_offs[-1]): int(rp.tree_offs[-1]) + 1]
             if self.device.type == "cuda":     # one launch (dp_stats.hip)
-                check(kernels().r2_dp_local_stats(ptr(root), ptr(rp.n_valid), ptr(self.probs), B,
-                                                  ptr(self.dp_send), stream_handle()), "dp_local_stats")
+                check(kernels().r2_dp_local_stats(ptr(root), ptr(rp.n_valid), ptr(S["probs"]), B,
+                                                  ptr(S["dp_send"]), stream_handle()), "dp_local_stats")
             else:
                 from ..parallel.sharded_replay import local_stats
-                local_stats(root, rp.n_valid, self.probs, out=self.dp_send)
+                local_stats(root, rp.n_valid, S["probs"], out=S["dp_send"])
 
     def _sample_dst(self, i: int):
         """Sample set ``i`` and the stored-state gathers (hs_cs, row offset, h out, c out) of its
@@ -1647,8 +1803,13 @@ class LearnerEngine:
         self.steps_done += 1
 
     def capture(self, warmup: int = 2):
-        """Capture the step into HIP graphs.  world == 1: one graph for the whole step.
-        world > 1: four graphs (core fwd/bwd | conv bwd | priorities | update) with the two
+        """Capture the step into HIP graphs.  world == 1: one graph for the whole step (hoisted:
+        one per variant).  world > 1 with dist.hoist_dp: the hoisted DP step's segment graphs
+        (``_capture_hoist_dp``: sample | forward to the heads | TD + BPTT + side branch + join |
+        conv bwd | update, every (sample set, 'P' / 'H', due) variant a step can ask for, none
+        captured inside a step loop), the collectives issued between them as ``dp_hoist_plan``
+        orders them; the one graph per variant follows after dist.one_graph_warm steps (RCCL).
+        world > 1 otherwise: four graphs (core fwd/bwd | conv bwd | priorities | update) with the two
         bucket all-reduces issued between them on the communication stream; with global
         sampling the core graph is split after the sampling launch and again before the heads /
         TD (six graphs): the 12-byte shard-stats all-gather runs on its own stream beside the
@@ -1662,6 +1823,15 @@ class LearnerEngine:
         torch.cuda.synchronize(self.device)
         self.graphs = []
         self._one_dp_graph = False
+        if self.hoist and self.dp:
+            # the hoisted DP step (dist.hoist_dp): the segment graphs of every variant now; the one
+            # graph per variant replaces them after dist.one_graph_warm steps (RCCL only)
+            self._make_rollout()
+            self._cgraph = None
+            self._capture_hoist_dp()
+            torch.cuda.synchronize(self.device)
+            self.graph = True
+            return
         if self.hoist:
             # the hoisted step's graph variants: (sample set, sampled by the previous step or
             # not, target sync due) -- all eight captured now, none inside a timed loop
@@ -1690,17 +1860,8 @@ class LearnerEngine:
             torch.cuda.synchronize(self.device)
             self.graph = True
             return
-        one = self.cfg.dist.graph_collectives and (self.world == 1 or self.cfg.dist.graph_collectives_multi)
         if self.dp:
-            # the segment graphs first; the whole DP step as ONE graph (collectives captured on
-            # their side streams) replaces them after dist.one_graph_warm steps and, at world > 1,
-            # a validation window (parallel/graph_rollout.py)
-            from ..parallel.graph_rollout import GraphRollout
-            dc = self.cfg.dist
-            self._rollout = GraphRollout(self.pg, self.rank, self.world,
-                                         enabled=one and self._pg_backend() == "nccl",
-                                         warm=int(dc.one_graph_warm), validate=int(dc.one_graph_validate),
-                                         device=self.device)
+            self._make_rollout()
         if self.dp:
             segs = [self._seg_core, self._seg_torso, self._seg_prio, self._seg_update]
             if self.dp_global:
@@ -1716,6 +1877,18 @@ class LearnerEngine:
             self.graphs.append(g)
         torch.cuda.synchronize(self.device)
         self.graph = True
+
+    def _make_rollout(self) -> None:
+        """The segment graphs first; the whole DP step as ONE graph (collectives captured on their
+        side streams) replaces them after dist.one_graph_warm steps and, at world > 1, a
+        validation window (parallel/graph_rollout.py)."""
+        from ..parallel.graph_rollout import GraphRollout
+        dc = self.cfg.dist
+        one = dc.graph_collectives and (self.world == 1 or dc.graph_collectives_multi)
+        self._rollout = GraphRollout(self.pg, self.rank, self.world,
+                                     enabled=one and self._pg_backend() == "nccl",
+                                     warm=int(dc.one_graph_warm), validate=int(dc.one_graph_validate),
+                                     device=self.device)
 
     def _capture_mode(self) -> str:
         """Graph capture error mode: with a process group the RCCL watchdog thread polls the events
@@ -1762,11 +1935,29 @@ class LearnerEngine:
     def _capture_one_dp(self) -> None:
         """The whole DP step in ONE graph: the bucket all-reduces and the shard-stats all-gather
         are captured on their side streams (fork / join as graph edges), so the ~15 us gap of
-        every segment boundary disappears."""
+        every segment boundary disappears.  The hoisted DP step (dist.hoist_dp): one such graph
+        per (sample set, 'P' / 'H', due) variant, the same collectives in the same order in each."""
         torch.cuda.synchronize(self.device)
+        pool = self.graphs[0].pool() if self.graphs else None
+        if self.hoist:
+            # one graph per (sample set, 'P' / 'H', due) variant of the hoisted DP step
+            cur, due0 = self._cur, getattr(self, "_hoist_due", False)
+            gs = {}
+            try:
+                for key in [(p, i, d) for p in (0, 1) for i in ("H", "P") for d in (False, True)]:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, pool=pool, capture_error_mode=self._capture_mode()):
+                        self._hoist_dp_body(*key)
+                    gs[key] = g
+            finally:
+                self._use_set(cur)
+                self._hoist_due = due0
+            torch.cuda.synchronize(self.device)
+            self._one_graphs = gs
+            self._one_dp_graph = True
+            return
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self.graphs[0].pool() if self.graphs else None,
-                              capture_error_mode=self._capture_mode()):
+        with torch.cuda.graph(g, pool=pool, capture_error_mode=self._capture_mode()):
             self._dp_step_body()
         torch.cuda.synchronize(self.device)
         self._one_graph = g
@@ -1779,13 +1970,14 @@ class LearnerEngine:
 
     def _dp_repair(self) -> None:
         """After a one-graph validation mismatch: every rank takes rank 0's weights and optimizer
-        state, and re-packs its kernel layouts."""
+        state, re-packs its kernel layouts and (hoisted DP step) drops the pre-sampled batch."""
         import torch.distributed as dist
         src = dist.get_global_rank(self.pg, 0) if hasattr(dist, "get_global_rank") else 0
         for t in (self.master, self.target, self.opt_a, self.opt_b):
             dist.broadcast(t, src=src, group=self.pg)
         self._pack(always=True)
         self._one_dp_graph = False
+        self.invalidate_hoist()     # the pre-sampled batch's target frames used the old weights
 
     def _dp_rollout_after_step(self) -> None:
         ro = getattr(self, "_rollout", None)

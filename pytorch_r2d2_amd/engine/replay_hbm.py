@@ -233,29 +233,38 @@ class HBMReplay:
 
     def prio_tail_sample(self, starts: torch.Tensor, B: int, upd_lo: int, upd_hi: int, out_idx,
                          out_prob, rows, Tn: int, states, h_f32: bool, qreset, skip_xcds: int = 0,
-                         stream=None, td_wait=None) -> bool:
+                         stream=None, td_wait=None, dp_out=None) -> bool:
         """prio_tail (ending the step) + the NEXT step's sample_batch in ONE launch (replay.hip
         r2_prio_tail_sample): the sample waits for the repaired tree inside the launch.  Same
         arguments as prio_tail + sample_batch; False (nothing launched) when the shape refuses.
         ``skip_xcds``: keep the launch's workgroups off the first XCDs (the BPTT recurrence's,
         lstm_persist.hip xcd_map 3) -- placement only, same results.  ``td_wait``: the TD
         launch's done flag (td.hip TdDuelArgs::done), which the tail then waits for on the device
-        and clears."""
+        and clears.  ``dp_out`` (3 floats; the hoisted data-parallel step): the launch's last
+        sampler workgroup also writes the sampled batch's shard stats [S_k, N_k, min_b q_k(b)]
+        there, the three floats of ``r2_dp_local_stats`` on ``out_prob`` (replay.hip
+        r2_prio_tail_sample_dp); without it the launch is the one it always was."""
         if self.tree.device.type != "cuda":
             return False
+        if dp_out is not None and (dp_out.dtype != torch.float32 or dp_out.numel() < 3
+                                   or not dp_out.is_contiguous() or dp_out.device != self.tree.device):
+            raise ValueError("prio_tail_sample: dp_out must be 3 contiguous fp32 values on the "
+                             "replay's device")
         rc = self.cfg.replay
         hs = np.asarray([ptr(s_[0]) for s_ in states] + [0], dtype=np.int64)
         off = np.asarray([int(s_[1]) for s_ in states] + [0], dtype=np.int32)
         h = np.asarray([ptr(s_[2]) for s_ in states] + [0], dtype=np.int64)
         c = np.asarray([ptr(s_[3]) for s_ in states] + [0], dtype=np.int64)
-        r = kernels().r2_prio_tail_sample(
+        k = kernels()
+        extra = () if dp_out is None else (ptr(self.n_valid), ptr(dp_out))
+        r = (k.r2_prio_tail_sample if dp_out is None else k.r2_prio_tail_sample_dp)(
             ptr(starts), B, ptr(self.is_start), ptr(self.priority), ptr(self.tree),
             self.tree_offs.ctypes.data, self.tree_sizes.ctypes.data, self.tree_levels, rc.seq_len,
             upd_lo, upd_hi, self.cap_e, float(rc.eta), ptr(self.dirty), ptr(self.dirty_count),
             self.max_dirty, ptr(self.prio_sync), ptr(self.step), self.seed, ptr(out_idx),
             ptr(out_prob), ptr(rows), Tn, self.H, len(states), hs.ctypes.data, off.ctypes.data,
             h.ctypes.data, c.ctypes.data, int(h_f32), ptr(qreset), int(skip_xcds), ptr(td_wait),
-            self._ts(stream))
+            *extra, self._ts(stream))
         if r in (-3, -4):
             return False
         check(r, "prio_tail_sample")

@@ -113,6 +113,8 @@ _SIGS = {
     "r2_lstm_probes": [],
     "r2_prio_tail_sample": [P, I, P, P, P, P, P, I, I, I, I, I, F, P, P, I, P, P, U64, P, P, P, I,
                             I, I, P, P, P, P, I, P, I, P, P],
+    "r2_prio_tail_sample_dp": [P, I, P, P, P, P, P, I, I, I, I, I, F, P, P, I, P, P, U64, P, P, P, I,
+                               I, I, P, P, P, P, I, P, I, P, P, P, P],
     "r2_prio_tail_pack": [P, I, P, P, P, P, P, I, I, I, I, I, F, P, P, I, P, P, I,
                           P, P, I64, P, P, P, I64, P, P, P, I64, I64, I64, P, P, I64, I64, I64, P],
     "r2_td_duel_set_trace": [P],

@@ -8,6 +8,12 @@ The DP step has two captured forms (engine/learner_engine.py ``capture``):
                segment boundaries' ~15 us each disappear (profiles/r03_force_dp_ab.txt: the DP
                machinery's overhead at one forced rank 1.180 -> 1.122 ms).
 
+With ``dist.hoist_dp`` (the hoisted step on DP ranks) both forms exist per step variant -- (sample
+set, sampled at the step start or by the previous step's side branch, target sync due) -- with the
+priority segment folded into the side branch of the TD / BPTT segment; every variant issues the
+same collectives in the same order (engine/learner_engine.py ``dp_hoist_plan``), so ranks that
+replay different variants of one step still pair up, and this rollout promotes all variants at once.
+
 No multi-rank RCCL run has validated the one-graph form on this hardware, so it is rolled out per
 run (round-6 verdict item 7; reference: a single learner, /root/reference/learner.py:19):
 
