@@ -107,14 +107,21 @@ __device__ __forceinline__ float init_prio(const ActArgs& a, float q_sel, float 
   return powf(fabsf(q_sel - y) + a.prio_eps, a.alpha);
 }
 
-// sum_k gamma^(s_k - from) r_k over the buffered steps s_k in [from, upto] of env e
+// sum_k gamma^(s_k - from) r_k over the buffered steps s_k in [from, upto] of env e.  Summed in
+// double and rounded once: rewards of both signs cancel, and an fp32 sum leaves an error of the
+// order of 2^-24 sum_k |gamma^k r_k| in a return (and in the TD error behind the initial
+// priority) that can be orders of magnitude smaller than that
 __device__ __forceinline__ float returns_from(const ActArgs& a, int e, long long from, long long upto) {
-  float R = 0.f;
+  double R = 0.0;
   for (int j = 0; j < a.n; ++j) {
     const long long st = a.h_step[(size_t)j * a.E + e];
-    if (st >= from && st <= upto && st >= 0) R += a.h_r[(size_t)j * a.E + e] * powf(a.gamma, (float)(st - from));
+    if (st >= from && st <= upto && st >= 0) {
+      double gk = 1.0;                       // gamma^(st - from), st - from < n
+      for (long long k = st - from; k > 0; --k) gk *= (double)a.gamma;
+      R += (double)a.h_r[(size_t)j * a.E + e] * gk;
+    }
   }
-  return R;
+  return (float)R;
 }
 
 __device__ __forceinline__ int argmax_row(const float* q, int A) {
