@@ -15,6 +15,11 @@ for weights).  Modes:
                                                memory rings DMA'd into the HBM replay)
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 main.py --mode native --config seaquest8
                                                8-GPU data-parallel learner, actors on every GPU
+  python main.py --mode eval --config pong --checkpoint save/10000_save.pt --episodes 2
+                                               score a checkpoint: eval.envs envs act greedily on
+                                               its online net, 2 episodes each (no training)
+  python main.py --mode native --config pong --steps 2000 --set eval.every=500
+                                               ... and score the live weights every 500 steps
   python main.py --mode inproc --config cartpole --steps 2000
                                                single process (CPU ok), CartPole plumbing config
 
@@ -32,7 +37,7 @@ from pytorch_r2d2_amd.config import get_config  # noqa: E402
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("-n", "--n_actors", type=int, default=1)
-    p.add_argument("--mode", choices=["compat", "native", "inproc"], default="compat")
+    p.add_argument("--mode", choices=["compat", "native", "inproc", "eval"], default="compat")
     p.add_argument("--config", default=None, help="preset: reference|cartpole|pong|atari57|seaquest8|dmlab30")
     p.add_argument("--steps", type=int, default=None, help="learner steps (default: run forever in compat)")
     p.add_argument("--env", default=None, help="override env name (synthetic|pong|cartpole)")
@@ -54,18 +59,28 @@ def build_parser():
                    help="native under torchrun: the last N ranks run GPU actor groups only and feed "
                         "the learner ranks (split topology, parallel/actor_ranks.py)")
     p.add_argument("--rounds", type=int, default=200, help="split topology: actor push rounds")
+    p.add_argument("--checkpoint", default=None,
+                   help="eval: reference (save/N_save.pt) or full-state checkpoint to score")
+    p.add_argument("--episodes", type=int, default=None, help="eval: episodes per env (eval.episodes_per_env)")
+    p.add_argument("--eval-eps", type=float, default=None, help="eval: epsilon (eval.epsilon, 0 = greedy)")
     return p
 
 
 def run(argv=None):
     args = build_parser().parse_args(argv)
     preset = args.config or ("cartpole" if args.mode == "inproc" else
-                             "pong" if args.mode == "native" else "reference")
+                             "pong" if args.mode in ("native", "eval") else "reference")
     overrides = dict(kv.split("=", 1) for kv in args.set)
     if args.env:
         overrides["env.name"] = args.env
     cfg = get_config(preset, **overrides)
-    if args.mode == "native" and args.actor_ranks > 0:
+    if args.mode == "eval":
+        if not args.checkpoint:
+            raise SystemExit("--mode eval needs --checkpoint PATH")
+        from pytorch_r2d2_amd.runner import run_eval
+        out = run_eval(cfg, args.checkpoint, episodes_per_env=args.episodes, epsilon=args.eval_eps,
+                       metrics_path=args.metrics)
+    elif args.mode == "native" and args.actor_ranks > 0:
         from pytorch_r2d2_amd.runner import run_split
         out = run_split(cfg, rounds=args.rounds, actor_ranks=args.actor_ranks, capacity=args.capacity)
         out = {k: v for k, v in out.items() if k not in ("engine", "replay")}
@@ -93,7 +108,8 @@ def run(argv=None):
         from pytorch_r2d2_amd.runner import run_compat
         out = run_compat(cfg, args.n_actors, steps=args.steps, actor_device=args.actor_device,
                          learner_device=args.device)
-    print({k: v for k, v in out.items() if k not in ("losses", "returns")} if isinstance(out, dict) else out)
+    quiet = ("losses", "returns", "lengths")
+    print({k: v for k, v in out.items() if k not in quiet} if isinstance(out, dict) else out)
     return out
 
 

@@ -86,6 +86,56 @@ class PackedWeights:
         self.load_flat(self.flat, version)
 
 
+def infer_nets(o, nets):
+    """Q values + next recurrent state of every net of ``nets`` ((key, weights) pairs) for the
+    current observations of ``o.env``: one launch per stage for ALL nets (torso multi-job,
+    x-projection GEMM, one LSTM step launch with a chain per net, head GEMM, dueling epilogue) --
+    the step is launch-bound at these batch sizes.  ``o`` (a BatchedActor with two nets, a
+    BatchedEvaluator with one) holds the per-key buffers Xn, xp, h_bf, c, h_bf_new, c_new,
+    h32_new, zh, q and the persistent LSTM's ctr / err words."""
+    k = kernels()
+    s = stream_handle()
+    E, H, L = o.E, o.H, o.layout
+    if o.fused_torso:
+        o._tjobs = np.asarray(
+            [[0, E, ptr(w.pk["conv1"]), ptr(w.pk["b1"]), ptr(w.pk["conv2"]), ptr(w.pk["b2"]),
+              ptr(w.pk["conv3"]), ptr(w.pk["b3"]), ptr(o.Xn[key]), 0, 0, 0] for key, w in nets],
+            dtype=np.int64)
+        torso_fwd_fused(o.env.frames.reshape(E, -1), o._tjobs, o.fwd_geom, o.n_workers, s)
+    else:
+        for key, w in nets:
+            torso_forward_library(o.env.frames.reshape(E, -1), None, L, w.flat, o.cfg.env,
+                                  o.cfg.model, o.Xn[key])
+    gemm(*[Gemm(o.Xn[key], w.pk["w_ih"].t(), o.xp[key], bias=w.lstm_b) for key, w in nets])
+    if o.lstm_step:
+        # plain step kernel (lstm.hip, <= 128 rows per chain): no inter-workgroup hand-off,
+        # so it runs on any CU subset; E > 128 is split into two row halves per net
+        Bc = E if E <= 128 else (E + 1) // 2
+        if E > 128 and (E % 2 or Bc > 128):
+            raise ValueError("step-kernel LSTM: E <= 128 or an even E <= 256")
+        G = o.layout.G
+        rows = [(r0, Bc) for r0 in range(0, E, Bc)]
+        o._chains = np.asarray(
+            [[ptr(o.xp[key]) + r0 * G * 4, ptr(w.pk["w_hh"]), ptr(o.h_bf[key]) + r0 * H * 2,
+              ptr(o.c[key]) + r0 * H * 4, ptr(o.h_bf_new[key]) + r0 * H * 2,
+              ptr(o.c_new[key]) + r0 * H * 4, ptr(o.h32_new[key]) + r0 * H * 4, 0, 0]
+             for key, w in nets for r0, _ in rows], dtype=np.int64)
+        check(k.r2_lstm_fwd(o._chains.ctypes.data, len(o._chains), Bc, 1, H, 0, s),
+              "lstm_step_kernel")
+    else:
+        o._chains = np.asarray(
+            [[ptr(o.xp[key]), ptr(w.pk["w_hh"]), ptr(o.h_bf[key]), ptr(o.c[key]),
+              ptr(o.h_bf_new[key]), ptr(o.c_new[key]), ptr(o.h32_new[key]), 0, 0]
+             for key, w in nets], dtype=np.int64)
+        check(k.r2_lstm_fwd_persist(o._chains.ctypes.data, len(nets), E, 1, H, ptr(o.ctr),
+                                    ptr(o.err), s), "lstm_step")
+    gemm(*[Gemm(o.h_bf_new[key], w.pk["head1"].t(), o.zh[key]) for key, w in nets])
+    o._djobs = np.asarray(
+        [[ptr(o.zh[key]), ptr(w.pk["head_b1"]), ptr(w.pk["head_w2"]), ptr(w.pk["head_b2"]),
+          ptr(o.q[key]), 0, E] for key, w in nets], dtype=np.int64)
+    check(k.r2_dueling_fwd_multi(o._djobs.ctypes.data, len(nets), o.A, L.HD, s), "dueling_fwd")
+
+
 class BatchedActor:
     def __init__(self, cfg: R2D2Config, replay: HBMReplay, env, online, target,
                  global_env_offset: int = 0, total_envs: Optional[int] = None, seed: int = 0):
@@ -236,52 +286,9 @@ class BatchedActor:
 
     # ------------------------------------------------------------------ inference
     def _infer(self):
-        """Q values + next recurrent state of both nets for the current observations: one launch
-        per stage for BOTH nets (torso multi-job, x-projection GEMM, 2-chain LSTM step, head
-        GEMM, dueling epilogue) -- the actor step is launch-bound at these batch sizes."""
-        k = kernels()
-        s = stream_handle()
-        E, H, L = self.E, self.H, self.layout
-        nets = (("on", self.online), ("tg", self.target))
-        if self.fused_torso:
-            self._tjobs = np.asarray(
-                [[0, E, ptr(w.pk["conv1"]), ptr(w.pk["b1"]), ptr(w.pk["conv2"]), ptr(w.pk["b2"]),
-                  ptr(w.pk["conv3"]), ptr(w.pk["b3"]), ptr(self.Xn[key]), 0, 0, 0] for key, w in nets],
-                dtype=np.int64)
-            torso_fwd_fused(self.env.frames.reshape(E, -1), self._tjobs, self.fwd_geom,
-                            self.n_workers, s)
-        else:
-            for key, w in nets:
-                torso_forward_library(self.env.frames.reshape(E, -1), None, L, w.flat, self.cfg.env,
-                                      self.cfg.model, self.Xn[key])
-        gemm(*[Gemm(self.Xn[key], w.pk["w_ih"].t(), self.xp[key], bias=w.lstm_b) for key, w in nets])
-        if self.lstm_step:
-            # plain step kernel (lstm.hip, <= 128 rows per chain): no inter-workgroup hand-off,
-            # so it runs on any CU subset; E > 128 is split into two row halves per net
-            Bc = E if E <= 128 else (E + 1) // 2
-            if E > 128 and (E % 2 or Bc > 128):
-                raise ValueError("step-kernel LSTM: E <= 128 or an even E <= 256")
-            G = self.layout.G
-            rows = [(r0, Bc) for r0 in range(0, E, Bc)]
-            self._chains = np.asarray(
-                [[ptr(self.xp[key]) + r0 * G * 4, ptr(w.pk["w_hh"]), ptr(self.h_bf[key]) + r0 * H * 2,
-                  ptr(self.c[key]) + r0 * H * 4, ptr(self.h_bf_new[key]) + r0 * H * 2,
-                  ptr(self.c_new[key]) + r0 * H * 4, ptr(self.h32_new[key]) + r0 * H * 4, 0, 0]
-                 for key, w in nets for r0, _ in rows], dtype=np.int64)
-            check(k.r2_lstm_fwd(self._chains.ctypes.data, len(self._chains), Bc, 1, H, 0, s),
-                  "lstm_step_kernel")
-        else:
-            self._chains = np.asarray(
-                [[ptr(self.xp[key]), ptr(w.pk["w_hh"]), ptr(self.h_bf[key]), ptr(self.c[key]),
-                  ptr(self.h_bf_new[key]), ptr(self.c_new[key]), ptr(self.h32_new[key]), 0, 0]
-                 for key, w in nets], dtype=np.int64)
-            check(k.r2_lstm_fwd_persist(self._chains.ctypes.data, 2, E, 1, H, ptr(self.ctr),
-                                        ptr(self.err), s), "lstm_step")
-        gemm(*[Gemm(self.h_bf_new[key], w.pk["head1"].t(), self.zh[key]) for key, w in nets])
-        self._djobs = np.asarray(
-            [[ptr(self.zh[key]), ptr(w.pk["head_b1"]), ptr(w.pk["head_w2"]), ptr(w.pk["head_b2"]),
-              ptr(self.q[key]), 0, E] for key, w in nets], dtype=np.int64)
-        check(k.r2_dueling_fwd_multi(self._djobs.ctypes.data, 2, self.A, L.HD, s), "dueling_fwd")
+        """Q values + next recurrent state of both nets for the current observations
+        (``infer_nets``)."""
+        infer_nets(self, (("on", self.online), ("tg", self.target)))
 
     # ------------------------------------------------------------------ one env step
     @property

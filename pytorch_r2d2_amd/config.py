@@ -267,6 +267,17 @@ class DistConfig:
 
 
 @dataclass
+class EvalConfig:
+    """Policy evaluation (evaluator.BatchedEvaluator; absent in the reference, which prints the
+    returns of its exploring actors)."""
+    envs: int = 64                    # evaluation envs (<= 256), each with its own episode quota
+    episodes_per_env: int = 1         # every env records its first K episodes
+    epsilon: float = 0.0              # 0 = greedy
+    every: int = 0                    # run_native: evaluate every N learner steps, 0 = off
+    seed: int = 12345                 # env and action-draw seed of the evaluation (added to cfg.seed)
+
+
+@dataclass
 class R2D2Config:
     name: str = "reference"
     env: EnvConfig = field(default_factory=EnvConfig)
@@ -275,6 +286,7 @@ class R2D2Config:
     learner: LearnerConfig = field(default_factory=LearnerConfig)
     actor: ActorConfig = field(default_factory=ActorConfig)
     dist: DistConfig = field(default_factory=DistConfig)
+    eval: EvalConfig = field(default_factory=EvalConfig)
     seed: int = 0
 
     def to_dict(self) -> Dict[str, Any]:

@@ -102,6 +102,9 @@ _SIGS = {
     "r2_actor_post": [P, P],
     "r2_actor_tail": [P, P],
     "r2_actor_args_bytes": [],
+    "r2_eval_act": [P, P],
+    "r2_eval_post": [P, P],
+    "r2_eval_args_bytes": [],
     "r2_pack_step": [P, P, I64, P, P, P, I64, P, P, P, I64, I64, I64, P, P, I64, P, I64, I64, P],
     "r2_pack_split": [P, P, P, I64, I64, P],
     "r2_torso_bwd_set_debug": [P],

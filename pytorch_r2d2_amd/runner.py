@@ -10,6 +10,8 @@
                    under the ``Supervisor`` (restarts crashed actors).
 ``run_split``   -- learner ranks + actor-only ranks: device-packed trajectory records over RCCL
                    send/recv, weights broadcast from learner rank 0 (parallel/actor_ranks.py).
+``run_eval``    -- evaluate a checkpoint: E envs act greedily on the online net, every env records
+                   its first K episodes (evaluator.BatchedEvaluator); no replay, no learner.
 ``run_inproc``  -- single process, CPU or GPU, host replay + torch learner + single-env actors
                    stepping inline (the CartPole plumbing config, tests).
 """
@@ -31,14 +33,19 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
                capacity: Optional[int] = None, resume: Optional[str] = None,
                concurrent: bool = False, actor_cus_per_xcd: int = 0, learner_priority: int = 0,
                beat=None,
-               check_every: int = 200, on_step=None) -> Dict:
+               check_every: int = 200, on_step=None, eval_every: Optional[int] = None) -> Dict:
     """``concurrent``: actor group and learner run simultaneously on disjoint CU sets
     (engine/concurrent.py; ``actor_steps_per_update`` env steps per learner step), else they
     alternate on one stream.  ``beat``: supervisor heartbeat; the persistent kernels' error word
     is checked every ``check_every`` steps (a hand-off timeout stops the run with an error).
     ``cfg.actor.clear_ahead`` > 0 (serial loop only, >= ``actor_steps_per_update``): the actor clears
     its starts that many rows ahead and the engine keeps its pre-sampled batches across the actor
-    steps (``LearnerEngine.cover_writes``); ``hoisted_steps`` in the result counts them."""
+    steps (``LearnerEngine.cover_writes``); ``hoisted_steps`` in the result counts them.
+    ``eval_every`` (default ``cfg.eval.every``; serial loop only) > 0: every that many learner steps
+    a ``BatchedEvaluator`` scores the live online weights on the learner's stream between two
+    steps (``cfg.eval``: envs, episodes per env, epsilon); it touches nothing of the replay, so the
+    training run is bit for bit the one without it.  Each evaluation is logged and printed as an
+    ``"eval"`` record and ``eval_returns`` in the result lists (step, mean_return)."""
     from .actor_batched import BatchedActor, engine_weights
     from .engine.learner_engine import LearnerEngine
     from .engine.replay_hbm import HBMReplay
@@ -48,6 +55,12 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
     from .utils.faults import Liveness
     from .utils.metrics import MetricsLogger
 
+    eval_every = int(cfg.eval.every if eval_every is None else eval_every)
+    if eval_every < 0:
+        raise ValueError("eval_every must be >= 0")
+    if eval_every > 0 and concurrent:
+        raise ValueError("evaluation during training runs on the serial loop only "
+                         "(eval_every / eval.every with concurrent=True)")
     ahead = int(cfg.actor.clear_ahead)
     if ahead > 0 and concurrent:
         raise ValueError("actor.clear_ahead is the serial loop's rule; the concurrent driver keeps "
@@ -116,6 +129,13 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
             drv.on_learner_step = on_step
     elif use_graph and cfg.actor.use_graph and actor.can_capture:
         actor.capture(warmup=1)
+    evaluator = None
+    if eval_every > 0:
+        from .evaluator import evaluator_from_config
+        evaluator = evaluator_from_config(cfg, dev, on)
+        if use_graph and cfg.actor.use_graph and evaluator.can_capture:
+            evaluator.capture()
+    eval_returns = []
     losses = []
     env0 = actor.env_steps
     t1 = time.perf_counter()
@@ -129,6 +149,10 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
             eng.step()
             if on_step is not None:
                 on_step(it)
+            if evaluator is not None and (it + 1) % eval_every == 0:
+                eval_returns.append((it + 1, _log_eval(evaluator.run(), mlog, info.is_main,
+                                                       step=it + 1, envs=evaluator.E,
+                                                       episodes_per_env=evaluator.K)))
         if check_every and (it + 1) % check_every == 0:
             eng.check_errors()
         if (it + 1) % log_every == 0 or it == steps - 1:
@@ -165,7 +189,8 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
            "env_steps_per_s": (actor.env_steps - env0) / train_s,
            "losses": losses, "returns": list(actor.finished_returns), "env_steps": actor.env_steps,
            "concurrent": bool(concurrent), "learner_cus": eng.n_cus,
-           "weights_version": drv.version if drv is not None else None}
+           "weights_version": drv.version if drv is not None else None,
+           "eval_returns": eval_returns}
     if eng.hoist:
         out["hoisted_steps"] = eng.hoisted_steps
     if checkpoint_dir and info.is_main:
@@ -177,6 +202,49 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
         if s_ is not None:
             s_.close()
     return out
+
+
+def _log_eval(res: Dict, mlog, echo: bool, **fields) -> float:
+    """Log / print the ``"eval"`` record of one evaluation (its tables left out); its mean return."""
+    rec = dict(fields, **{k: v for k, v in res.items() if k not in ("returns", "lengths")})
+    if mlog:
+        mlog.log("eval", **rec)
+    if echo:
+        print("[eval]", rec, flush=True)
+    return res["mean_return"]
+
+
+def run_eval(cfg: R2D2Config, checkpoint: str, episodes_per_env: Optional[int] = None, epsilon=None,
+             envs: Optional[int] = None, metrics_path: Optional[str] = None, device=None,
+             use_graph: bool = True, max_steps: Optional[int] = None) -> Dict:
+    """Evaluate the online net of ``checkpoint`` -- a reference checkpoint (``save/{n}_save.pt``,
+    ours or the reference's) or a full-state one (``full_last.pt``) -- on the synthetic env of
+    ``cfg``: ``cfg.eval.envs`` envs, every env's first ``episodes_per_env`` episodes, greedy unless
+    ``epsilon`` / ``cfg.eval.epsilon`` says otherwise.  Returns ``BatchedEvaluator.run``'s result
+    (mean / std / min / max return, mean length, episodes, env steps, ``complete`` and the (E, K)
+    tables) and logs it as an ``"eval"`` record."""
+    from .actor_batched import PackedWeights
+    from .engine.layout import ParamLayout
+    from .evaluator import evaluator_from_config
+    from .utils.metrics import MetricsLogger
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("run_eval needs a GPU: inference runs on the HIP kernels")
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    obj = torch.load(checkpoint, map_location="cpu", weights_only=True)
+    full = isinstance(obj, dict) and obj.get("format") == "pytorch_r2d2_amd.full.v1"
+    sd = obj["online"] if full else obj
+    w = PackedWeights(ParamLayout(cfg.model, cfg.env), dev)
+    w.load(sd, version=int(obj["step"]) if full else -1)
+    ev = evaluator_from_config(cfg, dev, w, episodes_per_env, epsilon, envs)
+    if use_graph and cfg.actor.use_graph and ev.can_capture:
+        ev.capture()
+    res = ev.run(max_steps=max_steps)
+    mlog = MetricsLogger(metrics_path) if metrics_path else None
+    _log_eval(res, mlog, True, checkpoint=str(checkpoint), envs=ev.E, episodes_per_env=ev.K)
+    if mlog:
+        mlog.close()
+    return res
 
 
 def run_split(cfg: R2D2Config, rounds: int = 200, actor_ranks: Optional[int] = None,
