@@ -24,7 +24,7 @@ from typing import Any, Dict, Optional
 
 @dataclass
 class EnvConfig:
-    name: str = "synthetic"          # synthetic | cartpole | pong | dmlab_synth
+    name: str = "synthetic"          # synthetic | cartpole | pong | dmlab_synth | pong_device
     action_repeat: int = 4            # env.py:15
     n_stacks: int = 4                 # env.py:15
     frame_h: int = 84
@@ -38,6 +38,11 @@ class EnvConfig:
     switch: int = 8
     cue_only_first: bool = False
     obs_dim: int = 4                  # vector envs (CartPole)
+    # pong_device (the native Pong-like game, pong_ref.py): first to ``pong_points``, at most
+    # ``pong_max_steps`` agent steps, the opponent idles a frame with probability lapse/256
+    pong_points: int = 21
+    pong_max_steps: int = 5000
+    pong_opp_lapse: int = 64
 
 
 @dataclass

@@ -84,14 +84,12 @@ def aggregate(returns, lengths, n_done, counted_steps: int) -> Dict:
 
 
 def make_eval_env(cfg: R2D2Config, device, n_envs: Optional[int] = None, seed: Optional[int] = None):
-    """The synthetic env of ``cfg`` for evaluation: every env starts at the beginning of an episode."""
-    from .envs.synthetic import VecSyntheticAtari
-    return VecSyntheticAtari(int(n_envs or cfg.eval.envs), device,
-                             seed=cfg.seed + cfg.eval.seed if seed is None else seed,
-                             episode_len=cfg.env.episode_len, n_actions=cfg.model.n_actions,
-                             n_stacks=cfg.env.channels_per_frame * cfg.env.n_stacks,
-                             shape=(cfg.env.frame_h, cfg.env.frame_w), switch=cfg.env.switch,
-                             cue_only_first=cfg.env.cue_only_first, randomize_start=False)
+    """The device env of ``cfg`` (``envs.make_device_env``) for evaluation: every env starts at the
+    beginning of an episode."""
+    from .envs import make_device_env
+    return make_device_env(cfg, int(n_envs or cfg.eval.envs), device,
+                           seed=cfg.seed + cfg.eval.seed if seed is None else seed,
+                           randomize_start=False)
 
 
 def evaluator_from_config(cfg: R2D2Config, device, online, episodes_per_env: Optional[int] = None,
@@ -223,13 +221,15 @@ class BatchedEvaluator:
         self.steps += 1
 
     def default_max_steps(self) -> Optional[int]:
-        L = getattr(self.env, "episode_len", None)
+        """K episodes of the env's fixed ``episode_len`` or, where episodes vary (VecPong), of its
+        ``max_episode_len``, plus one step."""
+        L = getattr(self.env, "episode_len", None) or getattr(self.env, "max_episode_len", None)
         return None if L is None else self.K * int(L) + 1
 
     @torch.no_grad()
     def run(self, max_steps: Optional[int] = None, poll_every: int = 64) -> Dict:
         """``reset`` (unless nothing was stepped since the last one), then step until every env has
-        recorded its K episodes or ``max_steps`` steps were taken (default K * env.episode_len + 1).  The device's episode count is read once
+        recorded its K episodes or ``max_steps`` steps were taken (default ``default_max_steps``).  The device's episode count is read once
         every ``poll_every`` steps, nothing else syncs.  Where the env has an ``episode_len`` the
         first read falls on step K * episode_len, the earliest at which envs that all start at the
         beginning of an episode can be complete."""

@@ -49,7 +49,7 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
     from .actor_batched import BatchedActor, engine_weights
     from .engine.learner_engine import LearnerEngine
     from .engine.replay_hbm import HBMReplay
-    from .envs.synthetic import VecSyntheticAtari
+    from .envs import make_device_env
     from .parallel.dist import init_distributed
     from .utils.checkpoint import save_full_checkpoint, save_reference_checkpoint
     from .utils.faults import Liveness
@@ -83,11 +83,7 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
     eng = LearnerEngine(cfg, replay, dev, rank=info.rank, world=info.world,
                         process_group=dist.group.WORLD if info.world > 1 else None,
                         n_cus=n_cus_learner, xcd_cus=xcd_cus)
-    env = VecSyntheticAtari(E, dev, seed=cfg.seed + 101 * info.rank, episode_len=cfg.env.episode_len,
-                            n_actions=cfg.model.n_actions,
-                            n_stacks=cfg.env.channels_per_frame * cfg.env.n_stacks,
-                            shape=(cfg.env.frame_h, cfg.env.frame_w), switch=cfg.env.switch,
-                            cue_only_first=cfg.env.cue_only_first)
+    env = make_device_env(cfg, E, dev, seed=cfg.seed + 101 * info.rank)
     start = 0
     if resume:
         from .utils.checkpoint import load_full_checkpoint, restore_rng
@@ -218,7 +214,7 @@ def run_eval(cfg: R2D2Config, checkpoint: str, episodes_per_env: Optional[int] =
              envs: Optional[int] = None, metrics_path: Optional[str] = None, device=None,
              use_graph: bool = True, max_steps: Optional[int] = None) -> Dict:
     """Evaluate the online net of ``checkpoint`` -- a reference checkpoint (``save/{n}_save.pt``,
-    ours or the reference's) or a full-state one (``full_last.pt``) -- on the synthetic env of
+    ours or the reference's) or a full-state one (``full_last.pt``) -- on the device env of
     ``cfg``: ``cfg.eval.envs`` envs, every env's first ``episodes_per_env`` episodes, greedy unless
     ``epsilon`` / ``cfg.eval.epsilon`` says otherwise.  Returns ``BatchedEvaluator.run``'s result
     (mean / std / min / max return, mean length, episodes, env steps, ``complete`` and the (E, K)
@@ -270,7 +266,7 @@ def run_split(cfg: R2D2Config, rounds: int = 200, actor_ranks: Optional[int] = N
     from .engine.layout import ParamLayout
     from .engine.learner_engine import LearnerEngine
     from .engine.replay_hbm import HBMReplay
-    from .envs.synthetic import VecSyntheticAtari
+    from .envs import make_device_env
     from .parallel.actor_ranks import TrajectoryPusher, TrajectoryReceiver, WeightLinks, split_roles
     from .parallel.dist import init_distributed
     from .utils.faults import Liveness
@@ -366,11 +362,7 @@ def run_split(cfg: R2D2Config, rounds: int = 200, actor_ranks: Optional[int] = N
         while wl.taken == 0:          # the initial snapshot
             if wl.poll() == 0:
                 time.sleep(0.0005)
-        env = VecSyntheticAtari(E, dev, seed=cfg.seed + 101 * info.rank, episode_len=cfg.env.episode_len,
-                                n_actions=cfg.model.n_actions,
-                                n_stacks=cfg.env.channels_per_frame * cfg.env.n_stacks,
-                                shape=(cfg.env.frame_h, cfg.env.frame_w), switch=cfg.env.switch,
-                                cue_only_first=cfg.env.cue_only_first)
+        env = make_device_env(cfg, E, dev, seed=cfg.seed + 101 * info.rank)
         idx = actors.index(info.rank)
         actor = BatchedActor(cfg, replay, env, w_on, w_tg, global_env_offset=idx * E,
                              total_envs=A * E, seed=cfg.seed + info.rank)

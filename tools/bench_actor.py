@@ -16,7 +16,7 @@ from pytorch_r2d2_amd.actor_batched import BatchedActor, engine_weights  # noqa:
 from pytorch_r2d2_amd.config import get_config  # noqa: E402
 from pytorch_r2d2_amd.engine.learner_engine import LearnerEngine  # noqa: E402
 from pytorch_r2d2_amd.engine.replay_hbm import HBMReplay  # noqa: E402
-from pytorch_r2d2_amd.envs.synthetic import VecSyntheticAtari  # noqa: E402
+from pytorch_r2d2_amd.envs import make_device_env  # noqa: E402
 
 
 def main():
@@ -28,18 +28,18 @@ def main():
     ap.add_argument("--capacity", type=int, default=1 << 18)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-loop", action="store_true")
+    ap.add_argument("--set", nargs="*", default=[], metavar="KEY=VALUE",
+                    help="config overrides, e.g. env.name=pong_device")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
-    out = {"metric": "actor_env_steps_per_sec", "config": args.config}
+    overrides = dict(kv.split("=", 1) for kv in args.set)
+    out = {"metric": "actor_env_steps_per_sec", "config": args.config, **overrides}
     for E in [int(v) for v in args.envs.split(",")]:
-        cfg = get_config(args.config, **{"actor.envs_per_actor": E})
+        cfg = get_config(args.config, **{**overrides, "actor.envs_per_actor": E})
         cap = (args.capacity // E) * E
         replay = HBMReplay(cfg, dev, capacity=cap, n_subrings=E)
         eng = LearnerEngine(cfg, replay, dev)
-        env = VecSyntheticAtari(E, dev, seed=1, episode_len=cfg.env.episode_len,
-                                n_actions=cfg.model.n_actions,
-                                n_stacks=cfg.env.channels_per_frame * cfg.env.n_stacks,
-                                shape=(cfg.env.frame_h, cfg.env.frame_w))
+        env = make_device_env(cfg, E, dev, seed=1)
         on, tg = engine_weights(eng)
         actor = BatchedActor(cfg, replay, env, on, tg, seed=3)
         for _ in range(args.warmup):
