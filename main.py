@@ -20,6 +20,10 @@ for weights).  Modes:
                                                its online net, 2 episodes each (no training)
   python main.py --mode native --config pong --steps 2000 --set eval.every=500
                                                ... and score the live weights every 500 steps
+  python main.py --mode native --config pong --steps 2000 --set actor.compute_dtype=fp32
+                                               ... acting in split precision (fp32 inference; also
+                                               with --concurrent, and eval.compute_dtype=fp32 for
+                                               --mode eval / eval.every)
   python main.py --mode inproc --config cartpole --steps 2000
                                                single process (CPU ok), CartPole plumbing config
 

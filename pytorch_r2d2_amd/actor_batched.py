@@ -15,7 +15,15 @@ GPU context with 4 blocking D2H copies per env step (actor.py:96-106, model.py:6
   eta-mixed priorities all happen on the device; rows are written straight into the learner's
   HBM replay (each env owns one sub-ring, so episodes are contiguous);
 * weights are read from the co-located learner's packed bf16 buffers (zero-copy "broadcast"
-  when actor and learner share a GPU), or from a versioned ``WeightPublisher`` slot.
+  when actor and learner share a GPU), or from a versioned ``WeightPublisher`` slot;
+* ``actor.compute_dtype="fp32"`` (default bf16) acts in split precision (csrc/split.h), the
+  learner's precision: the fused split torso straight over the env's frames, split-precision
+  x-projection and head GEMMs on hi / lo weight planes, the hand-off-free split LSTM step
+  (csrc/kernels/lstm_step_sp.hip) on the carried fp32 state, the fp32 dueling epilogue -- still one
+  launch per stage for both nets and one graph per env step.  The stored recurrent states, initial
+  priorities and greedy actions then come from an fp32-accurate policy instead of a ~1e-3-relative
+  one.  It needs the Atari 4x84x84 geometry, hidden <= 256 and weights with lo planes (an fp32
+  learner's live weights, or ``PackedWeights(split=True)``); anything else is refused at construction.
 
 No host synchronisation per step: the whole env step is device-only and replays as a HIP graph
 (``capture``); finished-episode returns land in a device ring drained when read.
@@ -32,8 +40,9 @@ from .config import R2D2Config, epsilon_ladder
 from .engine.layout import ParamLayout
 from .engine.replay_hbm import HBMReplay
 from .ops._lib import check, kernels, ptr, stream_handle
-from .ops.gemm import Gemm, gemm
-from .ops.torso_lib import fused_torso_fwd_geom, torso_forward_library, torso_fwd_fused
+from .ops.gemm import G5_CFGS, Gemm, gemm, gemm_sp, gemm_sp_ws_bytes
+from .ops.torso_lib import (fused_torso_fwd_geom, fused_torso_supported, torso_forward_library,
+                            torso_fwd_fused)
 
 
 _VP = ctypes.c_void_p
@@ -58,17 +67,27 @@ class ActArgs(ctypes.Structure):
 
 class PackedWeights:
     """Own packed bf16/fp32 kernel-layout copy of a QNet (for actors not co-located with the
-    learner).  ``load(state_dict)`` / ``load_flat(flat)`` repack on device."""
+    learner).  ``load(state_dict)`` / ``load_flat(flat)`` repack on device.  ``split``: hold the
+    bf16 layouts as (2, bf_numel) hi / lo planes (csrc/split.h, filled by ``r2_pack_split``):
+    ``pk`` views the hi planes, ``pk_lo`` the lo planes (``None`` without ``split``) -- what fp32
+    inference (``compute_dtype="fp32"``) reads."""
 
-    def __init__(self, layout: ParamLayout, device):
+    def __init__(self, layout: ParamLayout, device, split: bool = False):
         self.L = layout
+        self.split = bool(split)
         d = torch.device(device)
         self.flat = torch.zeros(layout.padded, dtype=torch.float32, device=d)
-        self.bf = torch.zeros(layout.bf_numel, dtype=torch.bfloat16, device=d)
+        nb = (2, layout.bf_numel) if self.split else (layout.bf_numel,)
+        self.bf = torch.zeros(nb, dtype=torch.bfloat16, device=d)
         self.f32 = torch.zeros(layout.f_numel, dtype=torch.float32, device=d)
         self.bf_index = layout.bf_index.to(d)
         self.f_index = layout.f_index.to(d)
-        self.pk = layout.packed_views(self.bf, self.f32)
+        if self.split:
+            self.pk = layout.packed_views(self.bf[0], self.f32)
+            self.pk_lo = layout.packed_views(self.bf[1], self.f32)
+        else:
+            self.pk = layout.packed_views(self.bf, self.f32)
+            self.pk_lo = None
         self.lstm_b = torch.zeros(layout.G, dtype=torch.float32, device=d)
         self.version = -1
 
@@ -76,7 +95,11 @@ class PackedWeights:
         self.flat.copy_(flat)
         k = kernels()
         s = stream_handle()
-        check(k.r2_pack_bf16(ptr(self.flat), ptr(self.bf_index), ptr(self.bf), self.L.bf_numel, s), "pack")
+        n = self.L.bf_numel
+        if self.split:
+            check(k.r2_pack_split(ptr(self.flat), ptr(self.bf_index), ptr(self.bf), n, n, s), "pack_split")
+        else:
+            check(k.r2_pack_bf16(ptr(self.flat), ptr(self.bf_index), ptr(self.bf), n, s), "pack")
         check(k.r2_gather_f32(ptr(self.flat), ptr(self.f_index), ptr(self.f32), self.L.f_numel, s), "gather")
         torch.add(self.pk["b_ih"], self.pk["b_hh"], out=self.lstm_b)
         self.version = version
@@ -86,13 +109,110 @@ class PackedWeights:
         self.load_flat(self.flat, version)
 
 
+COMPUTE_DTYPES = ("bf16", "fp32")
+
+
+def check_compute_dtype(knob: str, value, cfg: R2D2Config, nets=()) -> bool:
+    """Validate an inference ``compute_dtype`` knob (``actor.compute_dtype`` /
+    ``eval.compute_dtype``) against the configuration and the weights it would read; True for
+    fp32.  Every refusal is a ``ValueError`` that names the knob."""
+    if value not in COMPUTE_DTYPES:
+        raise ValueError(f"{knob} must be 'bf16' or 'fp32', not {value!r}")
+    if value != "fp32":
+        return False
+    if not fused_torso_supported(cfg.env, cfg.model):
+        e = cfg.env
+        raise ValueError(f"{knob}=fp32 needs the fused split-precision torso (conv torso on 4x84x84 "
+                         f"frames), not torso {cfg.model.torso!r} on "
+                         f"{e.channels_per_frame * e.n_stacks}x{e.frame_h}x{e.frame_w}")
+    if cfg.model.hidden not in (64, 128, 256):
+        raise ValueError(f"{knob}=fp32: the split-precision LSTM step covers model.hidden 64, 128 "
+                         f"or 256, not {cfg.model.hidden}")
+    for w in nets:
+        if getattr(w, "pk_lo", None) is None:
+            raise ValueError(f"{knob}=fp32 reads hi / lo weight planes; these weights have no lo planes "
+                             "(a bf16 learner's live weights, or PackedWeights without split=True)")
+    return True
+
+
+def alloc_infer_fp32(o, keys) -> None:
+    """The buffers only fp32 inference uses, on ``o`` (a BatchedActor / BatchedEvaluator): the lo
+    planes of the torso features and of the new h, fp32 head pre-activations, and the split-K
+    workspace + tickets of its two GEMM sites (``gemm_sp`` must not allocate inside a capture)."""
+    E, L, d = o.E, o.layout, o.device
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=d)  # noqa: E731
+    o.Xn_lo = {k: z(E, L.D, dt=torch.bfloat16) for k in keys}
+    o.h_lo_new = {k: z(E, o.H, dt=torch.bfloat16) for k in keys}
+    o.zh = {k: z(E, 2 * L.HD) for k in keys}
+    o.sp_ws = {}
+    if d.type != "cuda":
+        return
+    # sized for the automatic K splits of any CU count the group may be given (n_workers)
+    for site, (K, N) in (("xproj", (L.D, L.G)), ("heads", (o.H, 2 * L.HD))):
+        a, b, c = z(E, K, dt=torch.bfloat16), z(N, K, dt=torch.bfloat16).t(), z(E, N)
+        probs = [Gemm(a, b, c, a_lo=a, b_lo=b) for _ in keys]
+        need = max(gemm_sp_ws_bytes(probs, [0] * len(probs), cfg, n_cus)
+                   for cfg in range(len(G5_CFGS)) for n_cus in range(8, 257, 8))
+        o.sp_ws[site] = (z(max(need // 4, 1)), z(4096, dt=torch.int32))
+
+
+def _infer_nets_fp32(o, nets):
+    """Split-precision inference (csrc/split.h): the learner's fp32 stages at actor shapes.  The
+    recurrence is the hand-off-free step kernel (lstm_step_sp.hip) whatever ``o.lstm_step`` says:
+    no persistent split kernel places an actor group's rows, and the step kernel runs on any CU
+    subset.  It reads the carried fp32 state (h32, c) as h0 / c0; ``h_bf`` is not used."""
+    k = kernels()
+    s = stream_handle()
+    E, H, L = o.E, o.H, o.layout
+    for _, w in nets:
+        if getattr(w, "pk_lo", None) is None:
+            raise ValueError("fp32 inference reads hi / lo weight planes; these weights have no lo planes")
+    fr = o.env.frames
+    if fr.dtype != torch.uint8 or not fr.is_contiguous():
+        raise ValueError("fp32 inference reads the env's frames in place: contiguous uint8")
+    o._tjobs = np.asarray(
+        [[0, E, ptr(w.pk["conv1"]), ptr(w.pk_lo["conv1"]), ptr(w.pk["b1"]), ptr(w.pk["conv2"]),
+          ptr(w.pk_lo["conv2"]), ptr(w.pk["b2"]), ptr(w.pk["conv3"]), ptr(w.pk_lo["conv3"]),
+          ptr(w.pk["b3"]), ptr(o.Xn[key]), ptr(o.Xn_lo[key]), 0, 0, 0, 0, 0, 0, 0]
+         for key, w in nets], dtype=np.int64)
+    check(k.r2_torso_fwd_sp_multi(ptr(fr), o._tjobs.ctypes.data, len(nets), o.n_workers, s),
+          "torso_fwd_sp_multi")
+    ws, tk = o.sp_ws["xproj"]
+    gemm_sp([Gemm(o.Xn[key], w.pk["w_ih"].t(), o.xp[key], bias=w.lstm_b, a_lo=o.Xn_lo[key],
+                  b_lo=w.pk_lo["w_ih"].t()) for key, w in nets],
+            splits=[0] * len(nets), ws=ws, tickets=tk, n_cus=o.n_workers)
+    # <= 128 rows per chain: E > 128 is split into two row halves per net (the bf16 step's rule)
+    Bc = E if E <= 128 else (E + 1) // 2
+    if E > 128 and (E % 2 or Bc > 128):
+        raise ValueError("step-kernel LSTM: E <= 128 or an even E <= 256")
+    G = L.G
+    o._chains = np.asarray(
+        [[ptr(o.xp[key]) + r0 * G * 4, ptr(w.pk["w_hh"]), ptr(o.h32[key]) + r0 * H * 4,
+          ptr(o.c[key]) + r0 * H * 4, ptr(o.h_bf_new[key]) + r0 * H * 2,
+          ptr(o.c_new[key]) + r0 * H * 4, ptr(o.h32_new[key]) + r0 * H * 4, 0, 0,
+          ptr(w.pk_lo["w_hh"]), ptr(o.h_lo_new[key]) + r0 * H * 2]
+         for key, w in nets for r0 in range(0, E, Bc)], dtype=np.int64)
+    check(k.r2_lstm_fwd_sp(o._chains.ctypes.data, len(o._chains), Bc, 1, H, 0, s), "lstm_step_sp")
+    ws, tk = o.sp_ws["heads"]
+    gemm_sp([Gemm(o.h_bf_new[key], w.pk["head1"].t(), o.zh[key], a_lo=o.h_lo_new[key],
+                  b_lo=w.pk_lo["head1"].t()) for key, w in nets],
+            splits=[0] * len(nets), ws=ws, tickets=tk, n_cus=o.n_workers)
+    o._djobs = np.asarray(
+        [[ptr(o.zh[key]), ptr(w.pk["head_b1"]), ptr(w.pk["head_w2"]), ptr(w.pk["head_b2"]),
+          ptr(o.q[key]), 0, E] for key, w in nets], dtype=np.int64)
+    check(k.r2_dueling_fwd_multi_f32(o._djobs.ctypes.data, len(nets), o.A, L.HD, s), "dueling_fwd_f32")
+
+
 def infer_nets(o, nets):
     """Q values + next recurrent state of every net of ``nets`` ((key, weights) pairs) for the
     current observations of ``o.env``: one launch per stage for ALL nets (torso multi-job,
     x-projection GEMM, one LSTM step launch with a chain per net, head GEMM, dueling epilogue) --
     the step is launch-bound at these batch sizes.  ``o`` (a BatchedActor with two nets, a
     BatchedEvaluator with one) holds the per-key buffers Xn, xp, h_bf, c, h_bf_new, c_new,
-    h32_new, zh, q and the persistent LSTM's ctr / err words."""
+    h32_new, zh, q and the persistent LSTM's ctr / err words.  ``o.sp`` (``compute_dtype`` fp32)
+    selects the split-precision stages (``_infer_nets_fp32``)."""
+    if getattr(o, "sp", False):
+        return _infer_nets_fp32(o, nets)
     k = kernels()
     s = stream_handle()
     E, H, L = o.E, o.H, o.layout
@@ -141,6 +261,9 @@ class BatchedActor:
                  global_env_offset: int = 0, total_envs: Optional[int] = None, seed: int = 0):
         """online/target: objects with ``pk`` (packed views) and ``lstm_b`` -- a LearnerEngine
         (use ``engine_weights(engine)``) or ``PackedWeights``."""
+        # inference precision (actor.compute_dtype): refused here, before anything is allocated
+        self.sp = check_compute_dtype("actor.compute_dtype", cfg.actor.compute_dtype, cfg,
+                                      (online, target))
         self.cfg, self.replay, self.env = cfg, replay, env
         self.online, self.target = online, target
         rc, m = cfg.replay, cfg.model
@@ -179,6 +302,8 @@ class BatchedActor:
         self.zh = {k: z(E, 2 * self.layout.HD, dt=torch.bfloat16) for k in ("on", "tg")}
         self.ctr = z(int(kernels().r2_lstm_persist_ctr_words()), dt=torch.int32)
         self.err = z(1, dt=torch.int32)
+        if self.sp:     # fp32 inference: lo planes, fp32 zh, the GEMM sites' split-K workspaces
+            alloc_infer_fp32(self, ("on", "tg"))
         # n-step history ring (device)
         # each env's history rows point into its own sub-ring (initially its first row), so the
         # masked scatters below never see two envs on one row
@@ -241,6 +366,8 @@ class BatchedActor:
 
     def set_weights(self, online, target) -> None:
         """Point inference at other packed weights (captured graphs must be re-captured)."""
+        check_compute_dtype("actor.compute_dtype", self.cfg.actor.compute_dtype, self.cfg,
+                            (online, target))
         self.online, self.target = online, target
         self.graphs = None
 
@@ -394,11 +521,13 @@ class BatchedActor:
 
 
 def engine_weights(engine):
-    """Adapter exposing a LearnerEngine's live online / target packed weights to an actor."""
+    """Adapter exposing a LearnerEngine's live online / target packed weights to an actor:
+    ``pk`` (the hi planes), ``pk_lo`` (the lo planes of an fp32 engine, ``None`` on a bf16 one),
+    ``lstm_b`` and the flat master."""
 
     class _W:
-        def __init__(self, pk, b, flat):
-            self.pk, self.lstm_b, self.flat = pk, b, flat
+        def __init__(self, pk, b, flat, pk_lo):
+            self.pk, self.lstm_b, self.flat, self.pk_lo = pk, b, flat, pk_lo
 
-    return (_W(engine.pk, engine.lstm_b, engine.master),
-            _W(engine.pk_t, engine.lstm_b_t, engine.target))
+    return (_W(engine.pk, engine.lstm_b, engine.master, engine.pk_lo),
+            _W(engine.pk_t, engine.lstm_b_t, engine.target, engine.pk_t_lo))

@@ -211,6 +211,11 @@ class ActorConfig:
     # so the hoisted learner step keeps the batch it pre-sampled across up to that many actor
     # steps (LearnerEngine.cover_writes).  Costs clear_ahead * envs sampleable starts.  0 = off.
     clear_ahead: int = 0
+    # inference of the batched actor group: "bf16" (bf16 operands, fp32 accumulate) | "fp32" (split
+    # precision, csrc/split.h: hi / lo weight planes, fp32 carried state into the recurrence; the
+    # Atari 4x84x84 geometry, hidden <= 256, weights with lo planes -- an fp32 learner's live weights
+    # or PackedWeights(split=True))
+    compute_dtype: str = "bf16"
 
 
 @dataclass
@@ -280,6 +285,7 @@ class EvalConfig:
     epsilon: float = 0.0              # 0 = greedy
     every: int = 0                    # run_native: evaluate every N learner steps, 0 = off
     seed: int = 12345                 # env and action-draw seed of the evaluation (added to cfg.seed)
+    compute_dtype: str = "bf16"       # the evaluator's inference: bf16 | fp32 (see actor.compute_dtype)
 
 
 @dataclass

@@ -78,7 +78,8 @@ class ConcurrentDriver:
         L = actor.layout
         self.stage_on = engine.master.detach().clone()
         self.stage_tg = engine.target.detach().clone()
-        self.w_on, self.w_tg = PackedWeights(L, dev), PackedWeights(L, dev)
+        sp = bool(getattr(actor, "sp", False))     # fp32 inference reads hi / lo planes
+        self.w_on, self.w_tg = PackedWeights(L, dev, split=sp), PackedWeights(L, dev, split=sp)
         self.w_on.load_flat(self.stage_on, 0)
         self.w_tg.load_flat(self.stage_tg, 0)
         self.version = 0

@@ -9,7 +9,9 @@ episodes to finish" would favour short episodes).
 
 * inference is the acting path of ``BatchedActor`` for one net (``actor_batched.infer_nets``:
   fused torso, x-projection GEMM, one LSTM step, head GEMM, dueling epilogue), i.e. the policy
-  that acts: bf16 operands.  Split-precision (fp32) inference is not offered here.
+  that acts: bf16 operands by default; ``eval.compute_dtype="fp32"`` runs the split-precision
+  stages (hi / lo weight planes, fp32 carried state into the recurrence) on weights that have lo
+  planes -- ``PackedWeights(split=True)`` or an fp32 learner's live weights.
 * the bookkeeping is two launches of csrc/kernels/eval.hip around the device env step; their
   oracle is ``eval_ref``.
 * nothing of ``HBMReplay`` is read or written, so an evaluation between two learner steps leaves
@@ -27,7 +29,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from .actor_batched import infer_nets
+from .actor_batched import alloc_infer_fp32, check_compute_dtype, infer_nets
 from .config import R2D2Config
 from .engine.layout import ParamLayout
 from .ops._lib import check, kernels, ptr, stream_handle
@@ -114,6 +116,8 @@ class BatchedEvaluator:
         self.E = E = int(env.E)
         self.K = K = int(episodes_per_env)
         eps = check_eval_params(E, K, epsilon)
+        # inference precision (eval.compute_dtype): bf16, or split precision on hi / lo weights
+        self.sp = check_compute_dtype("eval.compute_dtype", cfg.eval.compute_dtype, cfg, (online,))
         self.device = d = env.frames.device
         self.H, self.A = m.hidden, m.n_actions
         self.layout = ParamLayout(m, cfg.env)
@@ -134,6 +138,9 @@ class BatchedEvaluator:
         self.zh = one(z(E, 2 * self.layout.HD, dt=torch.bfloat16))
         self.ctr = z(int(kernels().r2_lstm_persist_ctr_words()), dt=torch.int32)
         self.err = z(1, dt=torch.int32)
+        self.n_workers = 256         # torso workgroups (grid-stride over frames)
+        if self.sp:     # fp32 inference: lo planes, fp32 zh, the GEMM sites' split-K workspaces
+            alloc_infer_fp32(self, ("on",))
         self.act = z(E, dt=torch.int64)
         self.ret = z(E, K)
         self.ep_len = z(E, K, dt=torch.int32)
@@ -144,13 +151,13 @@ class BatchedEvaluator:
         self.t_d = z(1, dt=torch.int64)
         self.ticket = z(1, dt=torch.int32)
         self.lstm_step = False       # True: the plain step kernel instead of the persistent one
-        self.n_workers = 256         # torso workgroups (grid-stride over frames)
         self.steps = 0               # host mirror of t_d
         self.graph = None
         self.reset()
 
     def set_weights(self, online) -> None:
         """Point inference at other packed weights; a captured graph is dropped."""
+        check_compute_dtype("eval.compute_dtype", self.cfg.eval.compute_dtype, self.cfg, (online,))
         self.online = online
         self.graph = None
 

@@ -880,3 +880,42 @@ def check_activations(label, gates, grid):
             us = max(us, _compare(label, f"sigmoid (gate {q})", got, _sig(x), np.full(x.shape, EPS_SIG),
                                   names=("b", "unit")))
     return us, ut
+
+
+# ------------------------------------------------------------------------------------------
+# the split-precision step kernel (csrc/kernels/lstm_step_sp.hip, r2_lstm_fwd_sp): its cases, shared
+# by tests/test_lstm_step_sp_cpu.py and tests/test_lstm_step_sp_gpu.py.  The oracle is
+# check_forward(sp=True) unchanged: its t > 0 bound also allows for the 19-bit hand-off word, which
+# this kernel does not use (it reads the stored planes), so that bound is looser, not wrong.
+
+STEP_SP_CASES = {
+    # name: H, B (rows per chain), T, save_from per chain, chains without gates / h32; ``halves``:
+    # the chains are nets x two row halves of 2 B-row buffers (pointer offsets, as infer_nets calls it)
+    "s_clamp":  dict(H=64, B=5, T=1, save_from=(0,)),                      # one partial M tile
+    "s_tile2":  dict(H=64, B=33, T=3, save_from=(0, 1), no_gates=(1,)),    # second tile partial
+    "s_full":   dict(H=64, B=128, T=1, save_from=(0,)),
+    "s_h128":   dict(H=128, B=40, T=2, save_from=(2, 0), no_h32=(0,)),     # the H = 128 instance
+    "s_halves": dict(H=256, B=65, T=1, save_from=(0, 0, 0, 0), no_gates=(1, 2, 3), halves=True),
+}
+
+
+def step_sp_case(name: str):
+    """Operands of step case ``name``.  Returns (spec, chains); with ``halves`` chains 2n and 2n + 1
+    are rows [0, B) and [B, 2B) of net n's operands (same w), and ``chain["net"]`` / ``["row0"]``
+    say where the chain lives in its net's buffers."""
+    spec = STEP_SP_CASES[name]
+    rng = _rng(name, 0)
+    H, B, T = spec["H"], spec["B"], spec["T"]
+    per = 2 if spec.get("halves") else 1
+    chains = []
+    for c, sf in enumerate(spec["save_from"]):
+        if c % per == 0:
+            w = _weights(rng, H)
+            x = rng.standard_normal((T, per * B, 4 * H)).astype(np.float32)
+            h0 = (0.3 * rng.standard_normal((per * B, H))).astype(np.float32)
+            c0 = (0.5 * rng.standard_normal((per * B, H))).astype(np.float32)
+        r0 = (c % per) * B
+        chains.append(dict(w=w, xproj=np.ascontiguousarray(x[:, r0:r0 + B]), h0=h0[r0:r0 + B].copy(),
+                           c0=c0[r0:r0 + B].copy(), save_from=sf, net=c // per, row0=r0,
+                           h32=c not in spec.get("no_h32", ()), gates=c not in spec.get("no_gates", ())))
+    return spec, chains

@@ -52,6 +52,7 @@ _SIGS = {
                       P, P, P, P, I, P, P, P, P, P, I, P, P, P],
     "r2_dueling_fwd_multi_f32": [P, I, I, I, P],
     "r2_lstm_fwd_tag_sp": [P, I, I, I, I, P, P, P, P],
+    "r2_lstm_fwd_sp": [P, I, I, I, I, I, P],
     "r2_lstm_bwd_tag_sp": [P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P],
     "r2_lstm_bwd_tag_sp_hg": [P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P,
                               P, P, P, P, P, P, P, I, I, I, P, P, P, P],

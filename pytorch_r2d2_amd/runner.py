@@ -230,7 +230,7 @@ def run_eval(cfg: R2D2Config, checkpoint: str, episodes_per_env: Optional[int] =
     obj = torch.load(checkpoint, map_location="cpu", weights_only=True)
     full = isinstance(obj, dict) and obj.get("format") == "pytorch_r2d2_amd.full.v1"
     sd = obj["online"] if full else obj
-    w = PackedWeights(ParamLayout(cfg.model, cfg.env), dev)
+    w = PackedWeights(ParamLayout(cfg.model, cfg.env), dev, split=cfg.eval.compute_dtype == "fp32")
     w.load(sd, version=int(obj["step"]) if full else -1)
     ev = evaluator_from_config(cfg, dev, w, episodes_per_env, epsilon, envs)
     if use_graph and cfg.actor.use_graph and ev.can_capture:
@@ -356,7 +356,8 @@ def run_split(cfg: R2D2Config, rounds: int = 200, actor_ranks: Optional[int] = N
     else:
         cap_e = max(2 * (K + W + rc.n_step), 512)
         replay = HBMReplay(cfg, dev, capacity=cap_e * E, n_subrings=E)
-        w_on, w_tg = PackedWeights(L, dev), PackedWeights(L, dev)
+        sp = cfg.actor.compute_dtype == "fp32"     # fp32 inference reads hi / lo planes
+        w_on, w_tg = PackedWeights(L, dev, split=sp), PackedWeights(L, dev, split=sp)
         wl = WeightLinks(L.padded, dev, actors, learners[0], "actor", group=g_w)
         wl.attach(w_on, w_tg)
         while wl.taken == 0:          # the initial snapshot

@@ -5,6 +5,7 @@ same weights, in one process, the two alternating in windows of ``--steps`` grap
 actor windows is the yardstick for the difference).
 
     python tools/bench_eval.py --config atari57 --envs 64,256 --steps 300 --repeats 7
+    python tools/bench_eval.py --set actor.compute_dtype=fp32 eval.compute_dtype=fp32   (fp32 acting)
 Prints one JSON line; ``--out FILE`` also writes a table (profiles/eval_step_ab.txt)."""
 import argparse
 import json
@@ -42,17 +43,21 @@ def main():
     ap.add_argument("--capacity", type=int, default=1 << 18)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--set", nargs="*", default=[], metavar="KEY=VALUE",
+                    help="config overrides, e.g. actor.compute_dtype=fp32 eval.compute_dtype=fp32")
     args = ap.parse_args()
+    overrides = dict(kv.split("=", 1) for kv in args.set)
     dev = torch.device("cuda", 0)
     out = {"metric": "eval_vs_actor_ms_per_step", "config": args.config, "steps": args.steps,
            "repeats": args.repeats, "graph": not args.no_graph}
     lines = [f"# tools/bench_eval.py --config {args.config} --envs {args.envs} --steps {args.steps} "
-             f"--repeats {args.repeats}{' --no-graph' if args.no_graph else ''}",
+             f"--repeats {args.repeats}{' --no-graph' if args.no_graph else ''}"
+             f"{' --set ' + ' '.join(args.set) if args.set else ''}",
              "# ms per env step of all E envs, windows of --steps steps, actor and evaluator alternating",
              "# in one process; spread = max - min of the repeated windows",
              "# E     actor median (min .. max)        evaluator median (min .. max)     eval / actor"]
     for E in [int(v) for v in args.envs.split(",")]:
-        cfg = get_config(args.config, **{"actor.envs_per_actor": E})
+        cfg = get_config(args.config, **{**overrides, "actor.envs_per_actor": E})
         replay = HBMReplay(cfg, dev, capacity=(args.capacity // E) * E, n_subrings=E)
         eng = LearnerEngine(cfg, replay, dev)
         env = VecSyntheticAtari(E, dev, seed=1, episode_len=cfg.env.episode_len,
