@@ -5,9 +5,9 @@ GPU context with 4 blocking D2H copies per env step (actor.py:96-106, model.py:6
 §3.2, P2).  Here ONE actor group drives E environments on a GPU:
 
 * envs are vectorised on the device (``VecSyntheticAtari`` / ``VecCartPole``) or fed from CPU;
-* inference for all E envs and BOTH nets is a handful of launches: the fused uint8 torso kernel,
-  one x-projection GEMM per net, one LSTM step launch covering both nets (two chains), the head
-  GEMM + fused dueling epilogue;
+* inference for all E envs and BOTH nets is a handful of launches (``infer.PolicyInference``,
+  shared with the evaluator): the fused uint8 torso kernel, one x-projection GEMM per net, one
+  LSTM step launch covering both nets (two chains), the head GEMM + fused dueling epilogue;
 * epsilon-greedy with a per-env Ape-X ladder ``eps_i = 0.4^(1 + 7 i/(N-1))`` over the global env
   index (actor.py:22);
 * n-step returns, double-Q initial priorities (bootstrapped from Q(s_{t+n}), fixing Q5),
@@ -39,10 +39,8 @@ import torch
 from .config import R2D2Config, epsilon_ladder
 from .engine.layout import ParamLayout
 from .engine.replay_hbm import HBMReplay
+from .infer import COMPUTE_DTYPES, NetWeights, PolicyInference, check_compute_dtype  # noqa: F401
 from .ops._lib import check, kernels, ptr, stream_handle
-from .ops.gemm import G5_CFGS, Gemm, gemm, gemm_sp, gemm_sp_ws_bytes
-from .ops.torso_lib import (fused_torso_fwd_geom, fused_torso_supported, torso_forward_library,
-                            torso_fwd_fused)
 
 
 _VP = ctypes.c_void_p
@@ -67,7 +65,8 @@ class ActArgs(ctypes.Structure):
 
 class PackedWeights:
     """Own packed bf16/fp32 kernel-layout copy of a QNet (for actors not co-located with the
-    learner).  ``load(state_dict)`` / ``load_flat(flat)`` repack on device.  ``split``: hold the
+    learner), with the fields of ``NetWeights``: ``pk``, ``pk_lo``, ``lstm_b``, ``flat``.
+    ``load(state_dict)`` / ``load_flat(flat)`` repack on device.  ``split``: hold the
     bf16 layouts as (2, bf_numel) hi / lo planes (csrc/split.h, filled by ``r2_pack_split``):
     ``pk`` views the hi planes, ``pk_lo`` the lo planes (``None`` without ``split``) -- what fp32
     inference (``compute_dtype="fp32"``) reads."""
@@ -109,161 +108,13 @@ class PackedWeights:
         self.load_flat(self.flat, version)
 
 
-COMPUTE_DTYPES = ("bf16", "fp32")
-
-
-def check_compute_dtype(knob: str, value, cfg: R2D2Config, nets=()) -> bool:
-    """Validate an inference ``compute_dtype`` knob (``actor.compute_dtype`` /
-    ``eval.compute_dtype``) against the configuration and the weights it would read; True for
-    fp32.  Every refusal is a ``ValueError`` that names the knob."""
-    if value not in COMPUTE_DTYPES:
-        raise ValueError(f"{knob} must be 'bf16' or 'fp32', not {value!r}")
-    if value != "fp32":
-        return False
-    if not fused_torso_supported(cfg.env, cfg.model):
-        e = cfg.env
-        raise ValueError(f"{knob}=fp32 needs the fused split-precision torso (conv torso on 4x84x84 "
-                         f"frames), not torso {cfg.model.torso!r} on "
-                         f"{e.channels_per_frame * e.n_stacks}x{e.frame_h}x{e.frame_w}")
-    if cfg.model.hidden not in (64, 128, 256):
-        raise ValueError(f"{knob}=fp32: the split-precision LSTM step covers model.hidden 64, 128 "
-                         f"or 256, not {cfg.model.hidden}")
-    for w in nets:
-        if getattr(w, "pk_lo", None) is None:
-            raise ValueError(f"{knob}=fp32 reads hi / lo weight planes; these weights have no lo planes "
-                             "(a bf16 learner's live weights, or PackedWeights without split=True)")
-    return True
-
-
-def alloc_infer_fp32(o, keys) -> None:
-    """The buffers only fp32 inference uses, on ``o`` (a BatchedActor / BatchedEvaluator): the lo
-    planes of the torso features and of the new h, fp32 head pre-activations, and the split-K
-    workspace + tickets of its two GEMM sites (``gemm_sp`` must not allocate inside a capture)."""
-    E, L, d = o.E, o.layout, o.device
-    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=d)  # noqa: E731
-    o.Xn_lo = {k: z(E, L.D, dt=torch.bfloat16) for k in keys}
-    o.h_lo_new = {k: z(E, o.H, dt=torch.bfloat16) for k in keys}
-    o.zh = {k: z(E, 2 * L.HD) for k in keys}
-    o.sp_ws = {}
-    if d.type != "cuda":
-        return
-    # sized for the automatic K splits of any CU count the group may be given (n_workers)
-    for site, (K, N) in (("xproj", (L.D, L.G)), ("heads", (o.H, 2 * L.HD))):
-        a, b, c = z(E, K, dt=torch.bfloat16), z(N, K, dt=torch.bfloat16).t(), z(E, N)
-        probs = [Gemm(a, b, c, a_lo=a, b_lo=b) for _ in keys]
-        need = max(gemm_sp_ws_bytes(probs, [0] * len(probs), cfg, n_cus)
-                   for cfg in range(len(G5_CFGS)) for n_cus in range(8, 257, 8))
-        o.sp_ws[site] = (z(max(need // 4, 1)), z(4096, dt=torch.int32))
-
-
-def _infer_nets_fp32(o, nets):
-    """Split-precision inference (csrc/split.h): the learner's fp32 stages at actor shapes.  The
-    recurrence is the hand-off-free step kernel (lstm_step_sp.hip) whatever ``o.lstm_step`` says:
-    no persistent split kernel places an actor group's rows, and the step kernel runs on any CU
-    subset.  It reads the carried fp32 state (h32, c) as h0 / c0; ``h_bf`` is not used."""
-    k = kernels()
-    s = stream_handle()
-    E, H, L = o.E, o.H, o.layout
-    for _, w in nets:
-        if getattr(w, "pk_lo", None) is None:
-            raise ValueError("fp32 inference reads hi / lo weight planes; these weights have no lo planes")
-    fr = o.env.frames
-    if fr.dtype != torch.uint8 or not fr.is_contiguous():
-        raise ValueError("fp32 inference reads the env's frames in place: contiguous uint8")
-    o._tjobs = np.asarray(
-        [[0, E, ptr(w.pk["conv1"]), ptr(w.pk_lo["conv1"]), ptr(w.pk["b1"]), ptr(w.pk["conv2"]),
-          ptr(w.pk_lo["conv2"]), ptr(w.pk["b2"]), ptr(w.pk["conv3"]), ptr(w.pk_lo["conv3"]),
-          ptr(w.pk["b3"]), ptr(o.Xn[key]), ptr(o.Xn_lo[key]), 0, 0, 0, 0, 0, 0, 0]
-         for key, w in nets], dtype=np.int64)
-    check(k.r2_torso_fwd_sp_multi(ptr(fr), o._tjobs.ctypes.data, len(nets), o.n_workers, s),
-          "torso_fwd_sp_multi")
-    ws, tk = o.sp_ws["xproj"]
-    gemm_sp([Gemm(o.Xn[key], w.pk["w_ih"].t(), o.xp[key], bias=w.lstm_b, a_lo=o.Xn_lo[key],
-                  b_lo=w.pk_lo["w_ih"].t()) for key, w in nets],
-            splits=[0] * len(nets), ws=ws, tickets=tk, n_cus=o.n_workers)
-    # <= 128 rows per chain: E > 128 is split into two row halves per net (the bf16 step's rule)
-    Bc = E if E <= 128 else (E + 1) // 2
-    if E > 128 and (E % 2 or Bc > 128):
-        raise ValueError("step-kernel LSTM: E <= 128 or an even E <= 256")
-    G = L.G
-    o._chains = np.asarray(
-        [[ptr(o.xp[key]) + r0 * G * 4, ptr(w.pk["w_hh"]), ptr(o.h32[key]) + r0 * H * 4,
-          ptr(o.c[key]) + r0 * H * 4, ptr(o.h_bf_new[key]) + r0 * H * 2,
-          ptr(o.c_new[key]) + r0 * H * 4, ptr(o.h32_new[key]) + r0 * H * 4, 0, 0,
-          ptr(w.pk_lo["w_hh"]), ptr(o.h_lo_new[key]) + r0 * H * 2]
-         for key, w in nets for r0 in range(0, E, Bc)], dtype=np.int64)
-    check(k.r2_lstm_fwd_sp(o._chains.ctypes.data, len(o._chains), Bc, 1, H, 0, s), "lstm_step_sp")
-    ws, tk = o.sp_ws["heads"]
-    gemm_sp([Gemm(o.h_bf_new[key], w.pk["head1"].t(), o.zh[key], a_lo=o.h_lo_new[key],
-                  b_lo=w.pk_lo["head1"].t()) for key, w in nets],
-            splits=[0] * len(nets), ws=ws, tickets=tk, n_cus=o.n_workers)
-    o._djobs = np.asarray(
-        [[ptr(o.zh[key]), ptr(w.pk["head_b1"]), ptr(w.pk["head_w2"]), ptr(w.pk["head_b2"]),
-          ptr(o.q[key]), 0, E] for key, w in nets], dtype=np.int64)
-    check(k.r2_dueling_fwd_multi_f32(o._djobs.ctypes.data, len(nets), o.A, L.HD, s), "dueling_fwd_f32")
-
-
-def infer_nets(o, nets):
-    """Q values + next recurrent state of every net of ``nets`` ((key, weights) pairs) for the
-    current observations of ``o.env``: one launch per stage for ALL nets (torso multi-job,
-    x-projection GEMM, one LSTM step launch with a chain per net, head GEMM, dueling epilogue) --
-    the step is launch-bound at these batch sizes.  ``o`` (a BatchedActor with two nets, a
-    BatchedEvaluator with one) holds the per-key buffers Xn, xp, h_bf, c, h_bf_new, c_new,
-    h32_new, zh, q and the persistent LSTM's ctr / err words.  ``o.sp`` (``compute_dtype`` fp32)
-    selects the split-precision stages (``_infer_nets_fp32``)."""
-    if getattr(o, "sp", False):
-        return _infer_nets_fp32(o, nets)
-    k = kernels()
-    s = stream_handle()
-    E, H, L = o.E, o.H, o.layout
-    if o.fused_torso:
-        o._tjobs = np.asarray(
-            [[0, E, ptr(w.pk["conv1"]), ptr(w.pk["b1"]), ptr(w.pk["conv2"]), ptr(w.pk["b2"]),
-              ptr(w.pk["conv3"]), ptr(w.pk["b3"]), ptr(o.Xn[key]), 0, 0, 0] for key, w in nets],
-            dtype=np.int64)
-        torso_fwd_fused(o.env.frames.reshape(E, -1), o._tjobs, o.fwd_geom, o.n_workers, s)
-    else:
-        for key, w in nets:
-            torso_forward_library(o.env.frames.reshape(E, -1), None, L, w.flat, o.cfg.env,
-                                  o.cfg.model, o.Xn[key])
-    gemm(*[Gemm(o.Xn[key], w.pk["w_ih"].t(), o.xp[key], bias=w.lstm_b) for key, w in nets])
-    if o.lstm_step:
-        # plain step kernel (lstm.hip, <= 128 rows per chain): no inter-workgroup hand-off,
-        # so it runs on any CU subset; E > 128 is split into two row halves per net
-        Bc = E if E <= 128 else (E + 1) // 2
-        if E > 128 and (E % 2 or Bc > 128):
-            raise ValueError("step-kernel LSTM: E <= 128 or an even E <= 256")
-        G = o.layout.G
-        rows = [(r0, Bc) for r0 in range(0, E, Bc)]
-        o._chains = np.asarray(
-            [[ptr(o.xp[key]) + r0 * G * 4, ptr(w.pk["w_hh"]), ptr(o.h_bf[key]) + r0 * H * 2,
-              ptr(o.c[key]) + r0 * H * 4, ptr(o.h_bf_new[key]) + r0 * H * 2,
-              ptr(o.c_new[key]) + r0 * H * 4, ptr(o.h32_new[key]) + r0 * H * 4, 0, 0]
-             for key, w in nets for r0, _ in rows], dtype=np.int64)
-        check(k.r2_lstm_fwd(o._chains.ctypes.data, len(o._chains), Bc, 1, H, 0, s),
-              "lstm_step_kernel")
-    else:
-        o._chains = np.asarray(
-            [[ptr(o.xp[key]), ptr(w.pk["w_hh"]), ptr(o.h_bf[key]), ptr(o.c[key]),
-              ptr(o.h_bf_new[key]), ptr(o.c_new[key]), ptr(o.h32_new[key]), 0, 0]
-             for key, w in nets], dtype=np.int64)
-        check(k.r2_lstm_fwd_persist(o._chains.ctypes.data, len(nets), E, 1, H, ptr(o.ctr),
-                                    ptr(o.err), s), "lstm_step")
-    gemm(*[Gemm(o.h_bf_new[key], w.pk["head1"].t(), o.zh[key]) for key, w in nets])
-    o._djobs = np.asarray(
-        [[ptr(o.zh[key]), ptr(w.pk["head_b1"]), ptr(w.pk["head_w2"]), ptr(w.pk["head_b2"]),
-          ptr(o.q[key]), 0, E] for key, w in nets], dtype=np.int64)
-    check(k.r2_dueling_fwd_multi(o._djobs.ctypes.data, len(nets), o.A, L.HD, s), "dueling_fwd")
-
-
 class BatchedActor:
     def __init__(self, cfg: R2D2Config, replay: HBMReplay, env, online, target,
                  global_env_offset: int = 0, total_envs: Optional[int] = None, seed: int = 0):
-        """online/target: objects with ``pk`` (packed views) and ``lstm_b`` -- a LearnerEngine
-        (use ``engine_weights(engine)``) or ``PackedWeights``."""
+        """online/target: ``NetWeights`` of a LearnerEngine (``engine_weights(engine)``) or
+        ``PackedWeights``."""
         # inference precision (actor.compute_dtype): refused here, before anything is allocated
-        self.sp = check_compute_dtype("actor.compute_dtype", cfg.actor.compute_dtype, cfg,
-                                      (online, target))
+        check_compute_dtype("actor.compute_dtype", cfg.actor.compute_dtype, cfg, (online, target))
         self.cfg, self.replay, self.env = cfg, replay, env
         self.online, self.target = online, target
         rc, m = cfg.replay, cfg.model
@@ -277,33 +128,16 @@ class BatchedActor:
         self.T, self.stride = rc.seq_len, rc.overlap
         self.gamma = cfg.learner.gamma
         self.gamma_n = self.gamma ** self.n
-        self.layout = ParamLayout(m, cfg.env)
-        # fused torso forward: Atari 4x84x84 and DMLab-30 3x72x96 (else the library convs)
-        self.fwd_geom = fused_torso_fwd_geom(cfg.env, m) if self.device.type == "cuda" else None
-        self.fused_torso = self.fwd_geom is not None
         total = total_envs or E
         eps = [epsilon_ladder(global_env_offset + i, total, cfg.actor.eps_base, cfg.actor.eps_alpha)
                for i in range(E)]
         self.eps = torch.tensor(eps, dtype=torch.float32, device=d)
         # epsilon-greedy draws: counter-based hash of (seed, step, env) inside actor_pre_kernel
         self.seed = ((seed + 7919 * global_env_offset) * 0x9E3779B97F4A7C15 + 1) & ((1 << 64) - 1)
-        H, A, n = self.H, self.A, self.n
+        A, n = self.A, self.n
         z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=d)  # noqa: E731
-        # recurrent state of both nets: bf16 h (MFMA operand), fp32 h (stored state), fp32 c
-        self.h_bf = {k: z(E, H, dt=torch.bfloat16) for k in ("on", "tg")}
-        self.h32 = {k: z(E, H) for k in ("on", "tg")}
-        self.c = {k: z(E, H) for k in ("on", "tg")}
-        self.h_bf_new = {k: z(E, H, dt=torch.bfloat16) for k in ("on", "tg")}
-        self.h32_new = {k: z(E, H) for k in ("on", "tg")}
-        self.c_new = {k: z(E, H) for k in ("on", "tg")}
-        self.q = {k: z(E, A) for k in ("on", "tg")}
-        self.Xn = {k: z(E, self.layout.D, dt=torch.bfloat16) for k in ("on", "tg")}
-        self.xp = {k: z(E, self.layout.G) for k in ("on", "tg")}
-        self.zh = {k: z(E, 2 * self.layout.HD, dt=torch.bfloat16) for k in ("on", "tg")}
-        self.ctr = z(int(kernels().r2_lstm_persist_ctr_words()), dt=torch.int32)
-        self.err = z(1, dt=torch.int32)
-        if self.sp:     # fp32 inference: lo planes, fp32 zh, the GEMM sites' split-K workspaces
-            alloc_infer_fp32(self, ("on", "tg"))
+        # inference of both nets: its buffers, settings (lstm_step, n_workers) and launches
+        self.infer = PolicyInference(cfg, env, ("on", "tg"), "actor.compute_dtype", d)
         # n-step history ring (device)
         # each env's history rows point into its own sub-ring (initially its first row), so the
         # masked scatters below never see two envs on one row
@@ -341,11 +175,9 @@ class BatchedActor:
         self.env_steps = 0
         self.graphs = None
         # concurrent topology (engine/concurrent.py): start edits go to one of two pending lists
-        # (round parity) instead of the tree, and the LSTM runs as the plain step kernel (no
-        # persistent co-residency requirement on the actor's few CUs)
+        # (round parity) instead of the tree, and the LSTM runs as the plain step kernel
+        # (``infer.lstm_step``: no persistent co-residency requirement on the actor's few CUs)
         self.defer = None            # dict(pend=[2 x int32], cnt=[2 x int32], cap, D)
-        self.lstm_step = False
-        self.n_workers = 256         # torso workgroups (grid-stride over frames)
         # serial clear-ahead (actor.hip, ahead > 0): every step clears the start ``clear_ahead``
         # rows ahead of the write head instead of the row it overwrites, so a batch the learner
         # sampled before the next ``clear_ahead`` steps stays whole (LearnerEngine.cover_writes).
@@ -380,7 +212,7 @@ class BatchedActor:
         if self.replay.cap_e <= lookahead + self.T + self.n:
             raise ValueError(f"sub-ring of {self.replay.cap_e} rows too small for lookahead {lookahead}")
         self.defer = dict(pend=pend, cnt=cnt, cap=int(cap), D=int(lookahead))
-        self.lstm_step = True
+        self.infer.lstm_step = True
         self.graphs = None
 
     @property
@@ -414,13 +246,13 @@ class BatchedActor:
     # ------------------------------------------------------------------ inference
     def _infer(self):
         """Q values + next recurrent state of both nets for the current observations
-        (``infer_nets``)."""
-        infer_nets(self, (("on", self.online), ("tg", self.target)))
+        (``PolicyInference.run``)."""
+        self.infer.run((("on", self.online), ("tg", self.target)))
 
     # ------------------------------------------------------------------ one env step
     @property
     def can_capture(self) -> bool:
-        return (self.device.type == "cuda" and self.fused_torso
+        return (self.device.type == "cuda" and self.infer.fused_torso
                 and getattr(self.env, "capture_safe", False))
 
     def capture(self, warmup: int = 1):
@@ -462,14 +294,14 @@ class BatchedActor:
         self.env_steps += self.E
 
     def _args(self, wrap: bool, parity: int = 0) -> ActArgs:
-        rp, rc, lc = self.replay, self.cfg.replay, self.cfg.learner
+        rp, rc, lc, inf = self.replay, self.cfg.replay, self.cfg.learner, self.infer
         pre = rc.stored_state == "pre"
         a = ActArgs()
         for name, t in (("frames", rp.frames), ("obs", self.env.frames), ("hs_cs", rp.hs_cs),
                         ("ths_cs", rp.target_hs_cs), ("action", rp.action), ("reward", rp.reward),
                         ("done", rp.done), ("priority", rp.priority), ("is_start", rp.is_start),
                         ("leaves", rp.tree), ("n_valid", rp.n_valid), ("dirty", rp.dirty),
-                        ("dcount", rp.dirty_count), ("q_on", self.q["on"]), ("q_tg", self.q["tg"]),
+                        ("dcount", rp.dirty_count), ("q_on", inf.q["on"]), ("q_tg", inf.q["tg"]),
                         ("h_row", self.h_row), ("h_q", self.h_q), ("h_a", self.h_a), ("h_r", self.h_r),
                         ("h_step", self.h_step), ("h_valid", self.h_valid), ("ep_start", self.ep_start),
                         ("t", self.t_d), ("head", self.head_d), ("eps", self.eps), ("act", self.act),
@@ -477,10 +309,10 @@ class BatchedActor:
                         ("marks", self.marks)):
             setattr(a, name, ptr(t))
         for i, key in enumerate(("on", "tg")):
-            a.st_h[i] = ptr(self.h32[key] if pre else self.h32_new[key])
-            a.st_c[i] = ptr(self.c[key] if pre else self.c_new[key])
-            a.h_new[i], a.c_new[i] = ptr(self.h32_new[key]), ptr(self.c_new[key])
-            a.h32[i], a.c[i], a.h_bf[i] = ptr(self.h32[key]), ptr(self.c[key]), ptr(self.h_bf[key])
+            a.st_h[i] = ptr(inf.h32[key] if pre else inf.h32_new[key])
+            a.st_c[i] = ptr(inf.c[key] if pre else inf.c_new[key])
+            a.h_new[i], a.c_new[i] = ptr(inf.h32_new[key]), ptr(inf.c_new[key])
+            a.h32[i], a.c[i], a.h_bf[i] = ptr(inf.h32[key]), ptr(inf.c[key]), ptr(inf.h_bf[key])
         a.FB, a.seed = rp.frames.shape[1] if rp.frame_bytes else 0, self.seed
         a.E, a.A, a.H, a.n, a.T, a.stride = self.E, self.A, self.H, self.n, self.T, self.stride
         a.cap_e, a.W, a.wrap = rp.cap_e, self.T + self.n, int(wrap)
@@ -499,10 +331,7 @@ class BatchedActor:
         k = kernels()
         s = stream_handle()
         if self.cfg.actor.reset_state_every_step:   # ablation: memoryless acting
-            for key in ("on", "tg"):
-                self.h_bf[key].zero_()
-                self.h32[key].zero_()
-                self.c[key].zero_()
+            self.infer.zero_state()
         self._infer()
         a = self._args(wrap, parity)
         check(k.r2_actor_pre(ctypes.byref(a), s), "actor_pre")
@@ -521,13 +350,7 @@ class BatchedActor:
 
 
 def engine_weights(engine):
-    """Adapter exposing a LearnerEngine's live online / target packed weights to an actor:
-    ``pk`` (the hi planes), ``pk_lo`` (the lo planes of an fp32 engine, ``None`` on a bf16 one),
-    ``lstm_b`` and the flat master."""
-
-    class _W:
-        def __init__(self, pk, b, flat, pk_lo):
-            self.pk, self.lstm_b, self.flat, self.pk_lo = pk, b, flat, pk_lo
-
-    return (_W(engine.pk, engine.lstm_b, engine.master, engine.pk_lo),
-            _W(engine.pk_t, engine.lstm_b_t, engine.target, engine.pk_t_lo))
+    """A LearnerEngine's live online / target packed weights as ``NetWeights`` (``pk_lo``: the lo
+    planes of an fp32 engine, ``None`` on a bf16 one)."""
+    return (NetWeights(engine.pk, engine.pk_lo, engine.lstm_b, engine.master),
+            NetWeights(engine.pk_t, engine.pk_t_lo, engine.lstm_b_t, engine.target))

@@ -75,10 +75,10 @@ class ConcurrentDriver:
         self.cnt = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(2)]
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
         # the actor's own weights, re-packed from a staging slot the learner fills
-        L = actor.layout
+        L = actor.infer.layout
         self.stage_on = engine.master.detach().clone()
         self.stage_tg = engine.target.detach().clone()
-        sp = bool(getattr(actor, "sp", False))     # fp32 inference reads hi / lo planes
+        sp = actor.infer.sp                        # fp32 inference reads hi / lo planes
         self.w_on, self.w_tg = PackedWeights(L, dev, split=sp), PackedWeights(L, dev, split=sp)
         self.w_on.load_flat(self.stage_on, 0)
         self.w_tg.load_flat(self.stage_tg, 0)

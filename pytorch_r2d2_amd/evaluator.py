@@ -7,7 +7,7 @@ Ape-X epsilon ladder, produced while the replay is being written).  ``BatchedEva
 records the returns of its first ``episodes_per_env`` episodes (a per-env quota; "the first N
 episodes to finish" would favour short episodes).
 
-* inference is the acting path of ``BatchedActor`` for one net (``actor_batched.infer_nets``:
+* inference is the acting path of ``BatchedActor`` for one net (``infer.PolicyInference``:
   fused torso, x-projection GEMM, one LSTM step, head GEMM, dueling epilogue), i.e. the policy
   that acts: bf16 operands by default; ``eval.compute_dtype="fp32"`` runs the split-precision
   stages (hi / lo weight planes, fp32 carried state into the recurrence) on weights that have lo
@@ -29,11 +29,9 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from .actor_batched import alloc_infer_fp32, check_compute_dtype, infer_nets
 from .config import R2D2Config
-from .engine.layout import ParamLayout
+from .infer import PolicyInference, check_compute_dtype
 from .ops._lib import check, kernels, ptr, stream_handle
-from .ops.torso_lib import fused_torso_fwd_geom
 
 _VP = ctypes.c_void_p
 
@@ -106,8 +104,8 @@ def evaluator_from_config(cfg: R2D2Config, device, online, episodes_per_env: Opt
 class BatchedEvaluator:
     def __init__(self, cfg: R2D2Config, env, online, episodes_per_env: int = 1, epsilon=0.0,
                  seed: int = 0):
-        """online: an object with ``pk`` (packed views), ``lstm_b`` and ``flat`` -- a
-        ``PackedWeights`` or ``engine_weights(engine)[0]`` (the live weights)."""
+        """online: ``NetWeights`` -- a ``PackedWeights`` or ``engine_weights(engine)[0]`` (the live
+        weights)."""
         for name in ("frames", "step", "reset_all", "E"):
             if not hasattr(env, name):
                 raise TypeError(f"the env lacks {name!r} (the VecSyntheticAtari contract)")
@@ -117,30 +115,16 @@ class BatchedEvaluator:
         self.K = K = int(episodes_per_env)
         eps = check_eval_params(E, K, epsilon)
         # inference precision (eval.compute_dtype): bf16, or split precision on hi / lo weights
-        self.sp = check_compute_dtype("eval.compute_dtype", cfg.eval.compute_dtype, cfg, (online,))
+        check_compute_dtype("eval.compute_dtype", cfg.eval.compute_dtype, cfg, (online,))
         self.device = d = env.frames.device
         self.H, self.A = m.hidden, m.n_actions
-        self.layout = ParamLayout(m, cfg.env)
-        self.fwd_geom = fused_torso_fwd_geom(cfg.env, m) if d.type == "cuda" else None
-        self.fused_torso = self.fwd_geom is not None
         self.eps = torch.from_numpy(eps).to(d)
         self.seed = (int(seed) * 0x9E3779B97F4A7C15 + 0xE7A1) & ((1 << 64) - 1)
         if ctypes.sizeof(EvalArgs) != kernels().r2_eval_args_bytes():
             raise RuntimeError("EvalArgs layout differs from csrc/kernels/eval.hip")
-        H, A = self.H, self.A
         z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=d)  # noqa: E731
-        one = lambda t: {"on": t}  # noqa: E731  (infer_nets indexes its buffers by net key)
-        self.h_bf, self.h32, self.c = one(z(E, H, dt=torch.bfloat16)), one(z(E, H)), one(z(E, H))
-        self.h_bf_new, self.h32_new = one(z(E, H, dt=torch.bfloat16)), one(z(E, H))
-        self.c_new, self.q = one(z(E, H)), one(z(E, A))
-        self.Xn = one(z(E, self.layout.D, dt=torch.bfloat16))
-        self.xp = one(z(E, self.layout.G))
-        self.zh = one(z(E, 2 * self.layout.HD, dt=torch.bfloat16))
-        self.ctr = z(int(kernels().r2_lstm_persist_ctr_words()), dt=torch.int32)
-        self.err = z(1, dt=torch.int32)
-        self.n_workers = 256         # torso workgroups (grid-stride over frames)
-        if self.sp:     # fp32 inference: lo planes, fp32 zh, the GEMM sites' split-K workspaces
-            alloc_infer_fp32(self, ("on",))
+        # inference of the one net: its buffers, settings (lstm_step, n_workers) and launches
+        self.infer = PolicyInference(cfg, env, ("on",), "eval.compute_dtype", d)
         self.act = z(E, dt=torch.int64)
         self.ret = z(E, K)
         self.ep_len = z(E, K, dt=torch.int32)
@@ -150,7 +134,6 @@ class BatchedEvaluator:
         self.counted_steps = z(1, dt=torch.int64)
         self.t_d = z(1, dt=torch.int64)
         self.ticket = z(1, dt=torch.int32)
-        self.lstm_step = False       # True: the plain step kernel instead of the persistent one
         self.steps = 0               # host mirror of t_d
         self.graph = None
         self.reset()
@@ -165,22 +148,23 @@ class BatchedEvaluator:
         """Restart every env and forget everything recorded (a captured graph stays valid: it
         holds pointers only)."""
         self.env.reset_all()
-        for t in (self.h_bf["on"], self.h32["on"], self.c["on"], self.act, self.ret, self.ep_len,
-                  self.len, self.n_done, self.total_done, self.counted_steps, self.t_d, self.ticket):
+        self.infer.zero_state()
+        for t in (self.act, self.ret, self.ep_len, self.len, self.n_done, self.total_done,
+                  self.counted_steps, self.t_d, self.ticket):
             t.zero_()
         self.steps = 0
 
     # ------------------------------------------------------------------ one env step
     @property
     def can_capture(self) -> bool:
-        return (self.device.type == "cuda" and self.fused_torso
+        return (self.device.type == "cuda" and self.infer.fused_torso
                 and getattr(self.env, "capture_safe", False))
 
     def _args(self) -> EvalArgs:
-        a = EvalArgs()
-        for name, t in (("q", self.q["on"]), ("eps", self.eps), ("act", self.act),
-                        ("h_new", self.h32_new["on"]), ("c_new", self.c_new["on"]),
-                        ("h32", self.h32["on"]), ("c", self.c["on"]), ("h_bf", self.h_bf["on"]),
+        a, inf = EvalArgs(), self.infer
+        for name, t in (("q", inf.q["on"]), ("eps", self.eps), ("act", self.act),
+                        ("h_new", inf.h32_new["on"]), ("c_new", inf.c_new["on"]),
+                        ("h32", inf.h32["on"]), ("c", inf.c["on"]), ("h_bf", inf.h_bf["on"]),
                         ("ret", self.ret), ("ep_len", self.ep_len), ("len", self.len),
                         ("n_done", self.n_done), ("total_done", self.total_done),
                         ("counted_steps", self.counted_steps), ("t", self.t_d), ("ticket", self.ticket)):
@@ -193,7 +177,7 @@ class BatchedEvaluator:
         """One env step of all E envs, device-only (no host sync, capture-safe)."""
         k = kernels()
         s = stream_handle()
-        infer_nets(self, (("on", self.online),))
+        self.infer.run((("on", self.online),))
         a = self._args()
         check(k.r2_eval_act(ctypes.byref(a), s), "eval_act")
         reward, done, finished = self.env.step(self.act)

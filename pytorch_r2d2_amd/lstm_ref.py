@@ -890,7 +890,7 @@ def check_activations(label, gates, grid):
 
 STEP_SP_CASES = {
     # name: H, B (rows per chain), T, save_from per chain, chains without gates / h32; ``halves``:
-    # the chains are nets x two row halves of 2 B-row buffers (pointer offsets, as infer_nets calls it)
+    # the chains are nets x two row halves of 2 B-row buffers (pointer offsets, as PolicyInference.run calls it)
     "s_clamp":  dict(H=64, B=5, T=1, save_from=(0,)),                      # one partial M tile
     "s_tile2":  dict(H=64, B=33, T=3, save_from=(0, 1), no_gates=(1,)),    # second tile partial
     "s_full":   dict(H=64, B=128, T=1, save_from=(0,)),

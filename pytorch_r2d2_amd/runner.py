@@ -96,7 +96,7 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
                          total_envs=info.world * E, seed=cfg.seed + info.rank)
     if concurrent:
         # the actor group's kernels must never need co-residency on the learner's CUs
-        actor.lstm_step = True
+        actor.infer.lstm_step = True
     mlog = MetricsLogger(metrics_path, rank=info.rank) if metrics_path else None
     live = Liveness("learner", info.rank, beat)
     warm = warmup_rows if warmup_rows is not None else min(cfg.learner.initial_exploration,
@@ -115,7 +115,7 @@ def run_native(cfg: R2D2Config, steps: int = 1000, actor_steps_per_update: int =
     drv = None
     if concurrent:
         from .engine.concurrent import ConcurrentDriver
-        actor.n_workers = n_cus_actor
+        actor.infer.n_workers = n_cus_actor
         drv = ConcurrentDriver(eng, actor, steps_per_round=actor_steps_per_update,
                                actor_stream=s_act.stream if s_act else None,
                                learner_stream=s_learn.stream if s_learn else None,
@@ -369,7 +369,7 @@ def run_split(cfg: R2D2Config, rounds: int = 200, actor_ranks: Optional[int] = N
                              total_envs=A * E, seed=cfg.seed + info.rank)
         # an RCCL send may sit on this chip while the actor keeps stepping: the actor group's
         # kernels must never need co-residency of the whole grid
-        actor.lstm_step = True
+        actor.infer.lstm_step = True
         if use_graph and cfg.actor.use_graph and actor.can_capture:
             actor.capture(warmup=0)
         push = TrajectoryPusher(replay, K, feeds[info.rank], slots=int(dc.push_slots))

@@ -311,10 +311,10 @@ def test_batched_actor_replay_against_the_oracle(graph):
     for _ in range(N):
         log["obs"].append(_np(env.frames))
         actor.step()
-        log["q_on"].append(_np(actor.q["on"]))
-        log["q_tg"].append(_np(actor.q["tg"]))
-        log["h_new"].append(np.stack([_np(actor.h32_new[k]) for k in ("on", "tg")]))
-        log["c_new"].append(np.stack([_np(actor.c_new[k]) for k in ("on", "tg")]))
+        log["q_on"].append(_np(actor.infer.q["on"]))
+        log["q_tg"].append(_np(actor.infer.q["tg"]))
+        log["h_new"].append(np.stack([_np(actor.infer.h32_new[k]) for k in ("on", "tg")]))
+        log["c_new"].append(np.stack([_np(actor.infer.c_new[k]) for k in ("on", "tg")]))
         r, d, f = env.outputs()
         log["reward"].append(r)
         log["done"].append(d)
@@ -330,9 +330,9 @@ def test_batched_actor_replay_against_the_oracle(graph):
     got = {k: _np(v) for k, v in cols.items()}
     got["h_valid"] = _np(actor.h_valid).astype(np.uint8)
     got["marks"] = _np(actor.marks).reshape(actor.n + 2, E)
-    got["h32"] = np.stack([_np(actor.h32[k]) for k in ("on", "tg")])
-    got["c"] = np.stack([_np(actor.c[k]) for k in ("on", "tg")])
-    got["h_bf"] = np.stack([_np(actor.h_bf[k].view(torch.int16)).view(np.uint16) for k in ("on", "tg")])
+    got["h32"] = np.stack([_np(actor.infer.h32[k]) for k in ("on", "tg")])
+    got["c"] = np.stack([_np(actor.infer.c[k]) for k in ("on", "tg")])
+    got["h_bf"] = np.stack([_np(actor.infer.h_bf[k].view(torch.int16)).view(np.uint16) for k in ("on", "tg")])
     ar.check_exact(got, want, init)
     worst = dict(reward=ar.check_reward(got["reward"], want, sp, init["reward"]))
     worst.update(ar.check_priority(got["priority"], want, sp, init["priority"]))
@@ -396,11 +396,11 @@ def test_actor_inference_against_float64_qnet():
     nets = dict(zip(("on", "tg"), (_weights(cfg, 0), _weights(cfg, 1))))
     env = VecSyntheticAtari(E, DEV, seed=4, episode_len=3, randomize_start=False)
     actor = BatchedActor(cfg, rp, env, nets["on"][1], nets["tg"][1], seed=2)
-    assert actor.fused_torso
+    assert actor.infer.fused_torso
     worst = {}
     for step in range(6):
         frames = env.frames.cpu()
-        carried = {k: (actor.h32[k].cpu(), actor.c[k].cpu()) for k in nets}
+        carried = {k: (actor.infer.h32[k].cpu(), actor.infer.c[k].cpu()) for k in nets}
         if step == 3:
             assert all(not h.any() and not c.any() for h, c in carried.values()), "reset"
         elif step:
@@ -411,7 +411,7 @@ def test_actor_inference_against_float64_qnet():
             h, c = carried[k]
             exact = _qnet64(net, frames, h, c, False)
             emu = _qnet64(net, frames, h, c, True)
-            got = (actor.q[k], actor.h32_new[k], actor.c_new[k])
+            got = (actor.infer.q[k], actor.infer.h32_new[k], actor.infer.c_new[k])
             bound_q = None
             for nm, g, x, m in zip(("q", "h", "c"), got, exact, emu):
                 bound = 2.0 * float((m - x).abs().max())
@@ -422,7 +422,7 @@ def test_actor_inference_against_float64_qnet():
                 bound_q = bound if nm == "q" else bound_q
             top = exact[0].topk(2, dim=1)
             clear = (top.values[:, 0] - top.values[:, 1]) > bound_q
-            assert torch.equal(actor.q[k].cpu().argmax(dim=1)[clear], top.indices[:, 0][clear])
-            assert torch.equal(actor.h_bf_new[k].cpu(), actor.h32_new[k].cpu().bfloat16())
+            assert torch.equal(actor.infer.q[k].cpu().argmax(dim=1)[clear], top.indices[:, 0][clear])
+            assert torch.equal(actor.infer.h_bf_new[k].cpu(), actor.infer.h32_new[k].cpu().bfloat16())
     _REPORT.append("infer E 5, 6 steps      " + "  ".join(
         "%s %.3f (%.2e)" % (k, *worst[k]) for k in sorted(worst)))

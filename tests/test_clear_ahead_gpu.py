@@ -92,7 +92,7 @@ def test_actor_keeps_the_rows_ahead_of_its_head_free_of_starts(A, graph):
     # unfinished tail: the clear-ahead did not wipe the replay
     assert seen >= E * (CAP_E // cfg.replay.overlap) // 2
     _tree_consistent(rp)
-    assert int(actor.err.item()) == 0
+    assert int(actor.infer.err.item()) == 0
     assert rp.covered_written == rp.total_written == (300 + graph) * E
 
 
@@ -175,7 +175,7 @@ def test_covered_actor_writes_keep_the_hoist(graph, M):
     assert eng.error_word() == 0 and eng.guard_count() == 0
     eng.check_errors()
     _tree_consistent(rp)
-    assert int(actor.err.item()) == 0
+    assert int(actor.infer.err.item()) == 0
 
 
 # ------------------------------------------------------------------ 4. the serial order's numbers

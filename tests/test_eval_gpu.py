@@ -45,7 +45,7 @@ def _report():
     path = os.environ.get("R2D2_EVAL_ORACLE_REPORT")
     if path and _REPORT:
         with open(path, "w") as f:
-            f.write("# BatchedEvaluator inference (one net of actor_batched.infer_nets) against float64 QNet\n"
+            f.write("# BatchedEvaluator inference (one net of infer.PolicyInference) against float64 QNet\n"
                     "# per output: largest error / (2 x the error of the bf16-rounded float64 QNet),\n"
                     "#             and that error itself (1.0 = at the bound)\n")
             for line in _REPORT:
@@ -180,11 +180,11 @@ def test_evaluator_inference_against_float64_qnet():
     net, w = _weights(cfg, 0)
     env = VecSyntheticAtari(n, DEV, seed=4, episode_len=3, randomize_start=False)
     ev = BatchedEvaluator(cfg, env, w, episodes_per_env=2, seed=2)
-    assert ev.fused_torso
+    assert ev.infer.fused_torso
     worst = {}
     for step in range(6):
         frames = env.frames.cpu()
-        h, c = ev.h32["on"].cpu(), ev.c["on"].cpu()
+        h, c = ev.infer.h32["on"].cpu(), ev.infer.c["on"].cpu()
         if step in (0, 3):
             assert not h.any() and not c.any(), "reset"
         else:
@@ -193,7 +193,7 @@ def test_evaluator_inference_against_float64_qnet():
         torch.cuda.synchronize()
         exact = _qnet64(net, frames, h, c, False)
         emu = _qnet64(net, frames, h, c, True)
-        got = (ev.q["on"], ev.h32_new["on"], ev.c_new["on"])
+        got = (ev.infer.q["on"], ev.infer.h32_new["on"], ev.infer.c_new["on"])
         bound_q = None
         for nm, g, x, m in zip(("q", "h", "c"), got, exact, emu):
             bound = 2.0 * float((m - x).abs().max())
@@ -205,9 +205,9 @@ def test_evaluator_inference_against_float64_qnet():
         top = exact[0].topk(2, dim=1)
         clear = (top.values[:, 0] - top.values[:, 1]) > bound_q
         act = ev.act.cpu()
-        assert torch.equal(act, ev.q["on"].cpu().argmax(dim=1))
+        assert torch.equal(act, ev.infer.q["on"].cpu().argmax(dim=1))
         assert torch.equal(act[clear], top.indices[:, 0][clear])
-        assert torch.equal(ev.h_bf_new["on"].cpu(), ev.h32_new["on"].cpu().bfloat16())
+        assert torch.equal(ev.infer.h_bf_new["on"].cpu(), ev.infer.h32_new["on"].cpu().bfloat16())
     res = ev.result()
     assert res["complete"] and res["episodes"] == 2 * n and (res["lengths"] == 3).all()
     _REPORT.append("infer E 5, 6 steps      " + "  ".join("%s %.3f (%.2e)" % (k, *worst[k]) for k in sorted(worst)))
@@ -270,7 +270,7 @@ def test_epsilon_one_acts_at_random_and_zero_never_does():
     differs = 0
     for _ in range(16):
         ev.step()
-        act, greedy = ev.act.cpu(), ev.q["on"].cpu().argmax(dim=1)
+        act, greedy = ev.act.cpu(), ev.infer.q["on"].cpu().argmax(dim=1)
         assert act[0] == greedy[0]
         differs += int(act[1] != greedy[1])
     assert differs > 0

@@ -1,5 +1,5 @@
 """fp32 (split-precision) inference of the batched actor and the evaluator
-(``actor.compute_dtype`` / ``eval.compute_dtype`` = "fp32", actor_batched._infer_nets_fp32) on the
+(``actor.compute_dtype`` / ``eval.compute_dtype`` = "fp32", infer.PolicyInference._run_fp32) on the
 GPU: Q values and next states against float64 ``QNet`` under the project's split-precision bound,
 with the bf16-operand emulation as the control that must miss it; graph replay against eager
 steps; the replay rows the actor writes from the fp32 states; the evaluator's bookkeeping against
@@ -171,11 +171,11 @@ def test_actor_fp32_inference_against_float64_qnet(E):
     refs = {k: Refs(net) for k, (net, _) in nets.items()}
     env = VecSyntheticAtari(E, DEV, seed=4, episode_len=3, randomize_start=False)
     actor = BatchedActor(cfg, rp, env, nets["on"][1], nets["tg"][1], seed=2)
-    assert actor.sp and actor.fused_torso
+    assert actor.infer.sp and actor.infer.fused_torso
     worst = {}
     for step in range(6):
         frames = env.frames.cpu()
-        carried = {k: (actor.h32[k].cpu(), actor.c[k].cpu()) for k in nets}
+        carried = {k: (actor.infer.h32[k].cpu(), actor.infer.c[k].cpu()) for k in nets}
         if step == 3:
             assert all(not h.any() and not c.any() for h, c in carried.values()), "reset"
         elif step:
@@ -184,12 +184,12 @@ def test_actor_fp32_inference_against_float64_qnet(E):
         torch.cuda.synchronize()
         for k in nets:
             exact, bound, emu = refs[k].step(frames, *carried[k])
-            _check_outputs((f"E {E} step {step}", k), (actor.q[k], actor.h32_new[k], actor.c_new[k]),
+            _check_outputs((f"E {E} step {step}", k), (actor.infer.q[k], actor.infer.h32_new[k], actor.infer.c_new[k]),
                            exact, bound, emu, worst)
             top = exact[0].topk(2, dim=1)
             clear = (top.values[:, 0] - top.values[:, 1]) > bound[0]
-            assert torch.equal(actor.q[k].cpu().argmax(dim=1)[clear], top.indices[:, 0][clear])
-            _check_planes(actor, k)
+            assert torch.equal(actor.infer.q[k].cpu().argmax(dim=1)[clear], top.indices[:, 0][clear])
+            _check_planes(actor.infer, k)
     _report_line(f"actor E {E}, 6 steps", worst)
 
 
@@ -215,12 +215,12 @@ def test_captured_fp32_step_replays_bit_for_bit():
         log = []
         for _ in range(8):
             actor.step()
-            log += [actor.q[k].clone() for k in ("on", "tg")] + [actor.act.clone()]
+            log += [actor.infer.q[k].clone() for k in ("on", "tg")] + [actor.act.clone()]
         torch.cuda.synchronize()
         state = {f"log{i}": t for i, t in enumerate(log)}
         for k in ("on", "tg"):
-            state.update({f"h32_{k}": actor.h32[k], f"c_{k}": actor.c[k], f"h32_new_{k}": actor.h32_new[k],
-                          f"c_new_{k}": actor.c_new[k], f"h_lo_new_{k}": actor.h_lo_new[k]})
+            state.update({f"h32_{k}": actor.infer.h32[k], f"c_{k}": actor.infer.c[k], f"h32_new_{k}": actor.infer.h32_new[k],
+                          f"c_new_{k}": actor.infer.c_new[k], f"h_lo_new_{k}": actor.infer.h_lo_new[k]})
         state.update(frames=rp.frames, hs_cs=rp.hs_cs, ths_cs=rp.target_hs_cs, action=rp.action,
                      reward=rp.reward, done=rp.done, priority=rp.priority, is_start=rp.is_start,
                      tree=rp.tree, n_valid=rp.n_valid)
@@ -245,7 +245,7 @@ def test_fp32_actor_replay_rows_against_the_oracle():
     E, cap_e, N = 8, 60, 150
     cfg = get_config("atari57", **SMALL, **{"actor.compute_dtype": "fp32"})
     rp, env, actor = _actor(cfg, E, cap_e, env_cls=LogEnv)
-    assert cfg.replay.stored_state == "pre" and actor.sp
+    assert cfg.replay.stored_state == "pre" and actor.infer.sp
     rc, lc = cfg.replay, cfg.learner
     sp = ar.ActorSpec(E=E, A=actor.A, H=actor.H, n=actor.n, T=actor.T, stride=actor.stride, cap_e=cap_e,
                       FB=rp.frames.shape[1], R=actor.R, value_rescale=bool(lc.value_rescale),
@@ -264,13 +264,13 @@ def test_fp32_actor_replay_rows_against_the_oracle():
     for s in range(N):
         log["obs"].append(_np(env.frames))
         if s < 40:
-            carried.append(np.stack([np.concatenate([_np(actor.h32[k]), _np(actor.c[k])], axis=1)
+            carried.append(np.stack([np.concatenate([_np(actor.infer.h32[k]), _np(actor.infer.c[k])], axis=1)
                                      for k in ("on", "tg")]))
         actor.step()
-        log["q_on"].append(_np(actor.q["on"]))
-        log["q_tg"].append(_np(actor.q["tg"]))
-        log["h_new"].append(np.stack([_np(actor.h32_new[k]) for k in ("on", "tg")]))
-        log["c_new"].append(np.stack([_np(actor.c_new[k]) for k in ("on", "tg")]))
+        log["q_on"].append(_np(actor.infer.q["on"]))
+        log["q_tg"].append(_np(actor.infer.q["tg"]))
+        log["h_new"].append(np.stack([_np(actor.infer.h32_new[k]) for k in ("on", "tg")]))
+        log["c_new"].append(np.stack([_np(actor.infer.c_new[k]) for k in ("on", "tg")]))
         r, d, f = env.outputs()
         log["reward"].append(r)
         log["done"].append(d)
@@ -293,9 +293,9 @@ def test_fp32_actor_replay_rows_against_the_oracle():
     got = {k: _np(v) for k, v in cols.items()}
     got["h_valid"] = _np(actor.h_valid).astype(np.uint8)
     got["marks"] = _np(actor.marks).reshape(actor.n + 2, E)
-    got["h32"] = np.stack([_np(actor.h32[k]) for k in ("on", "tg")])
-    got["c"] = np.stack([_np(actor.c[k]) for k in ("on", "tg")])
-    got["h_bf"] = np.stack([_np(actor.h_bf[k].view(torch.int16)).view(np.uint16) for k in ("on", "tg")])
+    got["h32"] = np.stack([_np(actor.infer.h32[k]) for k in ("on", "tg")])
+    got["c"] = np.stack([_np(actor.infer.c[k]) for k in ("on", "tg")])
+    got["h_bf"] = np.stack([_np(actor.infer.h_bf[k].view(torch.int16)).view(np.uint16) for k in ("on", "tg")])
     ar.check_exact(got, want, init)
     worst = dict(reward=ar.check_reward(got["reward"], want, sp, init["reward"]))
     worst.update(ar.check_priority(got["priority"], want, sp, init["priority"]))
@@ -317,12 +317,12 @@ def test_fp32_evaluator_inference_and_bookkeeping():
     ref = Refs(net)
     env = LogEnv(n, DEV, seed=4, episode_len=3, randomize_start=False)
     ev = BatchedEvaluator(cfg, env, w, episodes_per_env=K, seed=2)
-    assert ev.sp and ev.fused_torso
+    assert ev.infer.sp and ev.infer.fused_torso
     worst = {}
     log = {k: [] for k in ("q", "h_new", "c_new", "reward", "done", "finished")}
     for step in range(6):
         frames = env.frames.cpu()
-        h, c = ev.h32["on"].cpu(), ev.c["on"].cpu()
+        h, c = ev.infer.h32["on"].cpu(), ev.infer.c["on"].cpu()
         if step in (0, 3):
             assert not h.any() and not c.any(), "reset"
         else:
@@ -330,21 +330,21 @@ def test_fp32_evaluator_inference_and_bookkeeping():
         ev.step()
         torch.cuda.synchronize()
         exact, bound, emu = ref.step(frames, h, c)
-        _check_outputs((f"eval step {step}", "on"), (ev.q["on"], ev.h32_new["on"], ev.c_new["on"]),
+        _check_outputs((f"eval step {step}", "on"), (ev.infer.q["on"], ev.infer.h32_new["on"], ev.infer.c_new["on"]),
                        exact, bound, emu, worst)
         top = exact[0].topk(2, dim=1)
         clear = (top.values[:, 0] - top.values[:, 1]) > bound[0]
         act = ev.act.cpu()
-        assert torch.equal(act, ev.q["on"].cpu().argmax(dim=1))
+        assert torch.equal(act, ev.infer.q["on"].cpu().argmax(dim=1))
         assert torch.equal(act[clear], top.indices[:, 0][clear])
-        _check_planes(ev, "on")
+        _check_planes(ev.infer, "on")
         r, d, f = env.outputs()
-        for k, v in (("q", _np(ev.q["on"])), ("h_new", _np(ev.h32_new["on"])), ("c_new", _np(ev.c_new["on"])),
+        for k, v in (("q", _np(ev.infer.q["on"])), ("h_new", _np(ev.infer.h32_new["on"])), ("c_new", _np(ev.infer.c_new["on"])),
                      ("reward", r), ("done", d), ("finished", f)):
             log[k].append(v)
         lg = er.EvalLogs(**{k: np.stack(v) for k, v in log.items()}, eps=_np(ev.eps), seed=ev.seed)
-        got = dict(act=_np(ev.act), h32=_np(ev.h32["on"]), c=_np(ev.c["on"]),
-                   h_bf=_np(ev.h_bf["on"].view(torch.int16)).view(np.uint16), ret=_np(ev.ret),
+        got = dict(act=_np(ev.act), h32=_np(ev.infer.h32["on"]), c=_np(ev.infer.c["on"]),
+                   h_bf=_np(ev.infer.h_bf["on"].view(torch.int16)).view(np.uint16), ret=_np(ev.ret),
                    ep_len=_np(ev.ep_len), n_done=_np(ev.n_done), len=_np(ev.len),
                    total_done=_np(ev.total_done), counted_steps=_np(ev.counted_steps), t=_np(ev.t_d))
         assert er.check(got, er.EvalRef(lg, K).at(step + 1)) == len(er.EXACT)
@@ -403,7 +403,7 @@ def _train(evaluate):
     ev = None
     if evaluate:
         ev = BatchedEvaluator(cfg, make_eval_env(cfg, DEV, 4), engine_weights(eng)[0], episodes_per_env=1)
-        assert ev.sp
+        assert ev.infer.sp
     for _ in range(6):
         eng.step()
         if ev is not None:
@@ -450,5 +450,5 @@ def test_run_native_with_an_fp32_actor(concurrent):
     assert all(np.isfinite(out["losses"])) and out["env_steps"] > 16 * 40
     if concurrent:
         drv = out["driver"]
-        assert drv.actor.sp and drv.w_on.pk_lo is not None
+        assert drv.actor.infer.sp and drv.w_on.pk_lo is not None
         assert drv.eng.error_word() == 0 and int(drv.err.item()) == 0

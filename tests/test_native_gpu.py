@@ -249,7 +249,7 @@ def _concurrent_setup(E=16, cap_e=512, M=2, masked=True, lookahead=None, driver=
     while int(rp.n_valid.item()) < 4 * cfg.learner.batch_size:
         actor.step()
     eng.capture(warmup=1)
-    actor.n_workers = na
+    actor.infer.n_workers = na
     drv = None
     if driver:
         drv = ConcurrentDriver(eng, actor, steps_per_round=M, lookahead=lookahead,
