@@ -504,6 +504,10 @@ extern "C" int r2_torso_bwd_geom(const uint8_t* frames, long long row_bytes, con
                                  int grid, const int* dst, const float* scale, float* grad, int cin,
                                  int h, int w, void* stream) {
   if (n <= 0) return 0;
+  // the kernels dereference every operand (rows included: the backward has no identity row list)
+  if (!frames || !rows || !act1 || !act2 || !dx3 || !out3 || !w3dg || !w2dg || !slab || !dst ||
+      !scale || !grad)
+    return -1;
   const bool atari = cin == 4 && h == 84 && w == 84, dm = cin == 3 && h == 72 && w == 96;
   if (!atari && !dm) return -6;
   const long long fb = (long long)cin * h * w;
