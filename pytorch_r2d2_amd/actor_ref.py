@@ -62,6 +62,7 @@ import numpy as np
 
 from . import replay_ref as rr
 from . import td_ref
+from .refnum import as_bytes, bf16_bits
 
 MUTATIONS = ("boot_argmax_tg", "terminal_bootstraps", "gamma_n_minus_1", "done_last_row_only",
              "no_final_start", "final_start_on_grid", "start_one_step_early", "last_max",
@@ -136,12 +137,6 @@ def h_inv32(x, eps):
     one, e = _f32(1.0), _f32(eps)
     s = (np.sqrt(one + _f32(4.0) * e * (np.abs(x) + one + e)) - one) / (_f32(2.0) * e)
     return (np.sign(x) * (s * s - one)).astype(_f32)
-
-
-def bf16_bits(x) -> np.ndarray:
-    """Round-to-nearest-even bf16 of finite float32 values, as uint16 bit patterns."""
-    b = np.ascontiguousarray(np.asarray(x, dtype=_f32)).view(np.uint32).astype(np.uint64)
-    return ((b + 0x7FFF + ((b >> 16) & 1)) >> 16).astype(np.uint16)
 
 
 def choose_actions(q_on, eps, seed: int, t: int, mutation: Optional[str] = None):
@@ -490,24 +485,20 @@ _ROW_MASK = dict(frames="row_w", hs_cs="row_w", ths_cs="row_w", action="row_w", 
                  ret_env="ret_w")
 
 
-def _bytes(x) -> np.ndarray:
-    return np.ascontiguousarray(x).view(np.uint8).reshape(-1)
-
-
 def _rows_equal(name, got, want, mask, init):
     """``got`` equals ``want`` bit for bit where ``mask`` (leading axes), ``init`` elsewhere."""
     want = np.asarray(want)
     got = np.asarray(got).reshape(want.shape)
     assert got.dtype == want.dtype, f"{name}: {got.dtype} vs oracle {want.dtype}"
     lead = mask.shape
-    g = _bytes(got).reshape(int(np.prod(lead)), -1)
-    w = _bytes(want).reshape(g.shape)
+    g = as_bytes(got).reshape(int(np.prod(lead)), -1)
+    w = as_bytes(want).reshape(g.shape)
     m = np.asarray(mask).reshape(-1)
     bad = np.flatnonzero(m & (g != w).any(axis=1))
     assert bad.size == 0, f"{name}: cells {bad[:8]} hold {got.reshape(g.shape[0], -1)[bad[:4]][:, :4]}, " \
                           f"oracle {want.reshape(g.shape[0], -1)[bad[:4]][:, :4]}"
     if init is not None:
-        i = _bytes(np.asarray(init).reshape(want.shape)).reshape(g.shape)
+        i = as_bytes(np.asarray(init).reshape(want.shape)).reshape(g.shape)
         bad = np.flatnonzero(~m & (g != i).any(axis=1))
         assert bad.size == 0, f"{name}: cells {bad[:8]} were written but the oracle says not yet"
 
@@ -544,7 +535,7 @@ def check_reward(got, want: dict, spec: ActorSpec, init=None) -> float:
     got = np.asarray(got, dtype=_f32).reshape(-1)
     fin = want["fin"]
     if init is not None:
-        keep = _bytes(got).reshape(-1, 4)[~fin] == _bytes(np.asarray(init, _f32)).reshape(-1, 4)[~fin]
+        keep = as_bytes(got).reshape(-1, 4)[~fin] == as_bytes(np.asarray(init, _f32)).reshape(-1, 4)[~fin]
         assert keep.all(), "reward: rows written that are not finalised"
     g = got[fin].astype(np.float64)
     assert np.isfinite(g).all(), "reward: finalised rows not written"
@@ -589,7 +580,7 @@ def check_priority(got, want: dict, spec: ActorSpec, init=None) -> dict:
     got = np.asarray(got, dtype=_f32).reshape(-1)
     fin = want["fin"]
     if init is not None:
-        keep = _bytes(got).reshape(-1, 4)[~fin] == _bytes(np.asarray(init, _f32)).reshape(-1, 4)[~fin]
+        keep = as_bytes(got).reshape(-1, 4)[~fin] == as_bytes(np.asarray(init, _f32)).reshape(-1, 4)[~fin]
         assert keep.all(), "priority: rows written that are not finalised"
     p = got[fin].astype(np.float64)
     assert np.isfinite(p).all() and (p > 0).all(), "priority: finalised rows not written or not positive"

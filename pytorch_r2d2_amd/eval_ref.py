@@ -33,7 +33,8 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from .actor_ref import bf16_bits, choose_actions
+from .actor_ref import choose_actions
+from .refnum import as_bytes, bf16_bits
 
 MUTATIONS = ("last_max", "past_quota", "no_state_reset", "t_twice")
 
@@ -113,10 +114,6 @@ EXACT = ("act", "h32", "c", "h_bf", "ret", "ep_len", "n_done", "len", "total_don
 _SCALARS = ("total_done", "counted_steps", "t")
 
 
-def _bytes(x) -> np.ndarray:
-    return np.ascontiguousarray(x).view(np.uint8).reshape(-1)
-
-
 def check(got: dict, want: dict, init: Optional[dict] = None) -> int:
     """Every item of ``got`` (host arrays of the kernels' dtypes) against ``EvalRef.at``, bit for
     bit; table cells and state the oracle says are not written yet must equal ``init``.  Returns
@@ -128,7 +125,7 @@ def check(got: dict, want: dict, init: Optional[dict] = None) -> int:
             continue
         if want.get(name) is None:           # act before the first step: not written
             if name in init:
-                assert np.array_equal(_bytes(got[name]), _bytes(init[name])), f"{name}: written before a step"
+                assert np.array_equal(as_bytes(got[name]), as_bytes(init[name])), f"{name}: written before a step"
             count += 1
             continue
         w = np.asarray(want[name])
@@ -148,13 +145,13 @@ def check(got: dict, want: dict, init: Optional[dict] = None) -> int:
         else:
             mask = np.ones(w.shape, bool)
         isz = g.dtype.itemsize
-        gb, wb = _bytes(g).reshape(-1, isz), _bytes(w).reshape(-1, isz)
+        gb, wb = as_bytes(g).reshape(-1, isz), as_bytes(w).reshape(-1, isz)
         m = np.broadcast_to(mask, w.shape).reshape(-1)
         bad = np.flatnonzero(m & (gb != wb).any(axis=1))
         assert bad.size == 0, (f"{name}: cells {bad[:8]} hold {g.reshape(-1)[bad[:8]]}, "
                                f"oracle {w.reshape(-1)[bad[:8]]}")
         if name in init:
-            ib = _bytes(np.asarray(init[name]).astype(g.dtype).reshape(w.shape)).reshape(-1, isz)
+            ib = as_bytes(np.asarray(init[name]).astype(g.dtype).reshape(w.shape)).reshape(-1, isz)
             bad = np.flatnonzero(~m & (gb != ib).any(axis=1))
             assert bad.size == 0, f"{name}: cells {bad[:8]} were written but the oracle says not yet"
         count += 1

@@ -24,6 +24,11 @@ from typing import Optional
 
 import numpy as np
 
+# bf16_val and the ownership checks are not used below: they stay part of this oracle's interface
+# (a caller that holds the oracle holds the checks of the buffers it describes)
+from .refnum import (bf16_bits, bf16_round, bf16_val, bits_equal, check_ownership,  # noqa: F401
+                     check_untouched, compare, compare_bf16, split_planes)
+
 U = 2.0 ** -24              # fp32 unit roundoff (round to nearest)
 UNITS, GCOLS = 16, 64       # hidden units / packed gate columns per workgroup (lstm.hip)
 DZ_K = 512                  # dz row length of the in-BPTT dh_ext path (lstm_bptt.hip PT_DZ_K)
@@ -60,31 +65,7 @@ MUTATIONS_BIAS = ("bias_tail_row", "bias_no_last_tile", "perm_inverse")
 
 
 # ------------------------------------------------------------------------------------------
-# number formats
-
-def bf16_bits(x) -> np.ndarray:
-    """fp32 -> bf16 bit patterns (uint16), round to nearest even; NaN stays NaN."""
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    b = x.view(np.uint32).astype(np.uint64)
-    r = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16).astype(np.uint16)
-    return np.where(np.isnan(x), np.uint16(0x7FC0), r)
-
-
-def bf16_val(bits) -> np.ndarray:
-    """bf16 bit patterns -> fp32 values."""
-    return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
-def bf16_round(x) -> np.ndarray:
-    return bf16_val(bf16_bits(x))
-
-
-def split_planes(x):
-    """csrc/split.h sp_split: hi = bf16(x), lo = bf16(x - hi), as fp32 values."""
-    x = np.asarray(x, dtype=np.float32)
-    hi = bf16_round(x)
-    return hi, bf16_round((x - hi).astype(np.float32))
-
+# the hand-off word (bf16 and the split planes: refnum.py)
 
 def round19(x) -> np.ndarray:
     """The 4-byte tagged hand-off word without its tag: fp32 rounded to 19 explicit mantissa bits,
@@ -202,65 +183,6 @@ def free_backward(dh_ext, gates, c_seq, c0, w, t0):
 
 
 # ------------------------------------------------------------------------------------------
-# comparison plumbing
-
-def _compare(label, tensor, got, ref, bound, names=("t", "b", "unit")):
-    """Largest |got - ref| / bound; raises naming the first element that is not finite or over its
-    bound."""
-    got = np.asarray(got, np.float64)
-    if got.size == 0:
-        return 0.0
-    with np.errstate(invalid="ignore", divide="ignore"):
-        use = np.abs(got - ref) / bound
-        use = np.where((got == ref) & np.isfinite(got), 0.0, use)
-    bad = ~(use <= 1.0)
-    if bad.any():
-        idx = tuple(int(i) for i in np.argwhere(bad)[0])
-        where = ", ".join(f"{n}={i}" for n, i in zip(names, idx))
-        raise AssertionError(f"{label}: {tensor}[{where}] = {got[idx]!r}, oracle {ref[idx]!r}, "
-                             f"bound {bound[idx]:.3e} (use {use[idx]:.3g}); {int(bad.sum())} elements fail")
-    return float(use.max())
-
-
-def _compare_bf16(label, tensor, bits, ref, bound, names=("t", "b", "unit")):
-    """A stored bf16 value against a reference whose *unrounded* value is known to ``bound``: rounding
-    is monotone, so the stored value is acceptable exactly when some x in [ref - bound, ref + bound]
-    rounds to it.  The use is the share of the bound that x needs: 0 where ref itself rounds to the
-    stored value, else the distance from ref to the rounding boundary of the stored value (the
-    midpoint between it and its bf16 neighbour on ref's side) over the bound.  Nothing is added
-    for the format, so the figure measures the arithmetic and not the rounding."""
-    bits = np.asarray(bits, np.uint16)
-    if bits.size == 0:
-        return 0.0
-    got = bf16_val(bits).astype(np.float64)
-    b = bits.astype(np.int64)
-    key = np.where(b < 0x8000, 0x8000 + b, 0x8000 - (b & 0x7FFF))      # monotone in the value
-    toward = np.where(got > ref, key - 1, key + 1)
-    nb = np.where(toward >= 0x8000, toward - 0x8000, 0x8000 | (0x8000 - toward)).astype(np.uint16)
-    mid = 0.5 * (got + bf16_val(nb).astype(np.float64))
-    with np.errstate(invalid="ignore", over="ignore"):
-        need = np.where(got > ref, mid - ref, np.where(got < ref, ref - mid, 0.0))
-        use = np.where(need <= 0.0, 0.0, need / (bound + 1e-300))
-        use = np.where(np.isfinite(got), use, np.inf)
-    bad = ~(use <= 1.0)
-    if bad.any():
-        idx = tuple(int(i) for i in np.argwhere(bad)[0])
-        where = ", ".join(f"{n}={i}" for n, i in zip(names, idx))
-        raise AssertionError(f"{label}: {tensor}[{where}] = {got[idx]!r} (bf16), oracle {ref[idx]!r} +- "
-                             f"{bound[idx]:.3e} before rounding (use {use[idx]:.3g}); {int(bad.sum())} elements fail")
-    return float(use.max())
-
-
-def _bits_equal(label, tensor, got, want, names=("t", "b", "unit")):
-    bad = np.asarray(got) != np.asarray(want)
-    if bad.any():
-        idx = tuple(int(i) for i in np.argwhere(bad)[0])
-        where = ", ".join(f"{n}={i}" for n, i in zip(names, idx))
-        raise AssertionError(f"{label}: {tensor}[{where}] = {got[idx]:#x}, expected {want[idx]:#x} "
-                             f"bit for bit; {int(bad.sum())} elements differ")
-
-
-# ------------------------------------------------------------------------------------------
 # forward: reference, bounds, check
 
 def forward_operands(ch, sp: bool):
@@ -345,25 +267,25 @@ def check_forward(label, ch, out, sp: bool, mutation: Optional[str] = None):
     T, B, H = out["c_seq"].shape
     sf = int(ch["save_from"]) + (1 if mutation == "save_from_off" else 0)
     uses = dict(gates=0.0, c=0.0, h=0.0, h_seq=0.0)
-    uses["c"] = _compare(label, "c_seq", out["c_seq"], ref["c"], ref["e_c"])
+    uses["c"] = compare(label, "c_seq", out["c_seq"], ref["c"], ref["e_c"])
     h32 = out.get("h32")
     if h32 is not None:
-        uses["h"] = _compare(label, "h32", h32, ref["h"], ref["e_h"])
+        uses["h"] = compare(label, "h32", h32, ref["h"], ref["e_h"])
         # bound-free: the stored planes are the roundings of the fp32 output, bit for bit
-        _bits_equal(label, "h_seq vs bf16(h32)", out["h_seq_bits"], bf16_bits(h32))
+        bits_equal(label, "h_seq vs bf16(h32)", out["h_seq_bits"], bf16_bits(h32))
         if sp:
             lo = bf16_bits((h32 - bf16_round(h32)).astype(np.float32))
-            _bits_equal(label, "h_seq_lo vs bf16(h32 - h_seq)", out["h_seq_lo_bits"], lo)
+            bits_equal(label, "h_seq_lo vs bf16(h32 - h_seq)", out["h_seq_lo_bits"], lo)
     if sp:    # hi = bf16(x) and lo = bf16(x - hi) for some x within e_h of the reference (x - hi is exact)
         hi = out["h_seq"].astype(np.float64)
-        uses["h_seq"] = max(_compare_bf16(label, "h_seq", out["h_seq_bits"], ref["h"], ref["e_h"]),
-                            _compare_bf16(label, "h_seq_lo", out["h_seq_lo_bits"], ref["h"] - hi, ref["e_h"]))
-    else:     # bf16 output: some value within e_h of the reference rounds to it (_compare_bf16)
-        uses["h_seq"] = _compare_bf16(label, "h_seq", out["h_seq_bits"], ref["h"], ref["e_h"])
+        uses["h_seq"] = max(compare_bf16(label, "h_seq", out["h_seq_bits"], ref["h"], ref["e_h"]),
+                            compare_bf16(label, "h_seq_lo", out["h_seq_lo_bits"], ref["h"] - hi, ref["e_h"]))
+    else:     # bf16 output: some value within e_h of the reference rounds to it (compare_bf16)
+        uses["h_seq"] = compare_bf16(label, "h_seq", out["h_seq_bits"], ref["h"], ref["e_h"])
     g = out.get("gates")
     if g is not None and sf < T and g.shape[0] > 0:
         n = min(g.shape[0], T - sf)
-        uses["gates"] = _compare(label, "gates", g[:n], ref["gates"][sf:sf + n], ref["e_gates"][sf:sf + n],
+        uses["gates"] = compare(label, "gates", g[:n], ref["gates"][sf:sf + n], ref["e_gates"][sf:sf + n],
                                  names=("t-save_from", "b", "packed col"))
         if mutation is None:
             # bound-free: c_seq[t] == f c_in + i g in fp32 from the saved gates and the stored c_in,
@@ -372,7 +294,7 @@ def check_forward(label, ch, out, sp: bool, mutation: Optional[str] = None):
             g64 = g.astype(np.float64)
             p1 = g64[..., col[1]] * ref["c_in"][sf:]
             p2 = g64[..., col[0]] * g64[..., col[2]]
-            _compare(label, "c_seq vs saved gates", out["c_seq"][sf:], p1 + p2,
+            compare(label, "c_seq vs saved gates", out["c_seq"][sf:], p1 + p2,
                      2.0 ** -23 * (np.abs(p1) + np.abs(p2)) + 1e-45)
     return uses
 
@@ -493,7 +415,7 @@ def stored_dgates(out, sp: bool):
 def check_backward(label, bw, out, sp: bool, mutation: Optional[str] = None, ref=None):
     """Gate gradients of every step against the teacher-forced reference.  The stored format adds
     its rounding: a bf16 plane is accepted exactly when some value x inside the bound rounds to it
-    (``_compare_bf16``); in split precision the lo plane likewise against x - hi, which fp32 holds
+    (``compare_bf16``); in split precision the lo plane likewise against x - hi, which fp32 holds
     exactly (csrc/split.h sp_lo).  No allowance is added for the formats.  Returns
     (largest use, reference dict)."""
     got = stored_dgates(out, sp)
@@ -502,10 +424,10 @@ def check_backward(label, bw, out, sp: bool, mutation: Optional[str] = None, ref
     names = ("t-t0", "b", "packed col")
     if sp:
         hi = out["dgates"].astype(np.float64)
-        use = max(_compare_bf16(label, "dgates", out["dgates_bits"], ref["dg"], ref["e_dg"], names=names),
-                  _compare_bf16(label, "dgates_lo", out["dgates_lo_bits"], ref["dg"] - hi, ref["e_dg"], names=names))
+        use = max(compare_bf16(label, "dgates", out["dgates_bits"], ref["dg"], ref["e_dg"], names=names),
+                  compare_bf16(label, "dgates_lo", out["dgates_lo_bits"], ref["dg"] - hi, ref["e_dg"], names=names))
     else:
-        use = _compare_bf16(label, "dgates", out["dgates_bits"], ref["dg"], ref["e_dg"], names=names)
+        use = compare_bf16(label, "dgates", out["dgates_bits"], ref["dg"], ref["e_dg"], names=names)
     return use, ref
 
 
@@ -534,9 +456,9 @@ def bias_reference(bw, ref, mutation: Optional[str] = None):
 def check_bias_grad(label, bw, out, ref, mutation: Optional[str] = None):
     """db1 against the reference within its bound; db2 == db1 bit for bit.  Returns the largest use."""
     db, e_db = bias_reference(bw, ref, mutation)
-    use = _compare(label, "db1", out["db1"], db, e_db, names=("gate row",))
+    use = compare(label, "db1", out["db1"], db, e_db, names=("gate row",))
     if out.get("db2") is not None:
-        _bits_equal(label, "db2 vs db1", np.asarray(out["db2"], np.float32).view(np.uint32),
+        bits_equal(label, "db2 vs db1", np.asarray(out["db2"], np.float32).view(np.uint32),
                     np.asarray(out["db1"], np.float32).view(np.uint32), names=("gate row",))
     return use
 
@@ -582,7 +504,7 @@ def head_grads_reference(hc, sp: bool, mutation: Optional[str] = None):
 def check_head_grads(label, hc, out, sp: bool, mutation: Optional[str] = None):
     """gw2 (1 + A, HD), gb2 (1 + A), gb1 (2 HD) against the reference.  Returns the largest use."""
     ref = head_grads_reference(hc, sp, mutation)
-    return max(_compare(label, n, out[n], *ref[n], names=("row", "col")[:np.ndim(out[n])] or ("i",))
+    return max(compare(label, n, out[n], *ref[n], names=("row", "col")[:np.ndim(out[n])] or ("i",))
                for n in ("gw2", "gb2", "gb1"))
 
 
@@ -605,33 +527,6 @@ def emulate_head_grads(hc, sp: bool):
         gb2 += dva[r]
         gb1 += dz[r]
     return dict(gw2=gw2, gb2=gb2, gb1=gb1)
-
-
-# ------------------------------------------------------------------------------------------
-# write ownership
-
-def check_ownership(label, tensor, full, pad: int, valid=None):
-    """``full``: a flat float view of a buffer that was NaN poison before the launch, ``pad`` guard
-    elements at each end.  The guards must still be poison, every element of the body where
-    ``valid`` (default: everywhere) must be finite, and every other body element still poison."""
-    full = np.asarray(full).reshape(-1)
-    body = full[pad:full.size - pad]
-    for name, g in (("guard before", full[:pad]), ("guard after", full[full.size - pad:])):
-        if not np.isnan(g).all():
-            i = int(np.argwhere(~np.isnan(g))[0, 0])
-            raise AssertionError(f"{label}: {tensor} {name} the buffer was written at {i} ({g[i]!r})")
-    v = np.ones(body.shape, bool) if valid is None else np.asarray(valid, bool).reshape(-1)
-    if not np.isfinite(body[v]).all():
-        i = int(np.argwhere(~np.isfinite(body) & v)[0, 0])
-        raise AssertionError(f"{label}: {tensor}[flat {i}] is not finite ({body[i]!r}): not written")
-    if not np.isnan(body[~v]).all():
-        i = int(np.argwhere(~np.isnan(body) & ~v)[0, 0])
-        raise AssertionError(f"{label}: {tensor}[flat {i}] = {body[i]!r} was written; the kernel does not own it")
-
-
-def check_untouched(label, tensor, full):
-    """A refused launch writes nothing: the whole buffer is still poison."""
-    check_ownership(label, tensor, full, 0, valid=np.zeros(np.asarray(full).size, bool))
 
 
 # ------------------------------------------------------------------------------------------
@@ -875,9 +770,9 @@ def check_activations(label, gates, grid):
         if not (np.isfinite(got).all() and (got >= lo).all() and (got <= 1.0).all()):
             raise AssertionError(f"{label}: gate {q} leaves [{lo}, 1] or is not finite")
         if q == 2:
-            ut = _compare(label, "tanh", got, np.tanh(x), np.full(x.shape, EPS_TANH), names=("b", "unit"))
+            ut = compare(label, "tanh", got, np.tanh(x), np.full(x.shape, EPS_TANH), names=("b", "unit"))
         else:
-            us = max(us, _compare(label, f"sigmoid (gate {q})", got, _sig(x), np.full(x.shape, EPS_SIG),
+            us = max(us, compare(label, f"sigmoid (gate {q})", got, _sig(x), np.full(x.shape, EPS_SIG),
                                   names=("b", "unit")))
     return us, ut
 

@@ -52,6 +52,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from .refnum import mix64
+
 H = W = 84
 N_ACTIONS = 6
 BG, LIT, AGENT, OPP = 87, 236, 147, 148
@@ -85,14 +87,6 @@ class PongRules:
     salt_serve: int = 3
     salt_dir: int = 4
     salt_start: int = 5
-
-
-def mix64(z):
-    """common.h r2_mix64 (the splitmix64 finaliser) on uint64 arrays, wrapping."""
-    z = z + np.uint64(0x9E3779B97F4A7C15)
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
 
 
 def env_hash(seed: int, a, b) -> np.ndarray:

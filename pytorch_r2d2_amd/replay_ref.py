@@ -32,12 +32,13 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
+from .refnum import as_u64, mix64
+
 MUTATIONS = ("wrap_prev_subring", "window_no_wrap", "range_hi_closed", "range_lo_closed",
              "mean_only", "max_only", "mean_64", "next_leaf", "n_valid_per_entry")
 
 U24 = 2.0 ** -24
 FANOUT = 64
-_M64 = (1 << 64) - 1
 
 
 # ------------------------------------------------------------------ geometry, RNG, CDF
@@ -54,24 +55,9 @@ def tree_geometry(cap: int):
     return offs, sizes
 
 
-def _u64(x) -> np.ndarray:
-    """At least 1-d uint64 array (array arithmetic wraps silently; Python ints are masked)."""
-    if isinstance(x, (int, np.integer)):
-        return np.asarray([int(x) & _M64], dtype=np.uint64)
-    return np.atleast_1d(np.asarray(x)).astype(np.uint64)
-
-
-def mix64(z) -> np.ndarray:
-    """common.h r2_mix64: the splitmix64 finaliser, wrapping 64-bit arithmetic."""
-    z = _u64(z) + np.uint64(0x9E3779B97F4A7C15)
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
-
-
 def uniform(seed: int, ctr: int, idx) -> np.ndarray:
     """common.h r2_uniform(seed, ctr, idx): the exact float32 value in [0, 1), one per ``idx``."""
-    z = mix64(_u64(seed) ^ mix64(_u64(ctr) * np.uint64(0x100000001B3) + _u64(idx)))
+    z = mix64(as_u64(seed) ^ mix64(as_u64(ctr) * np.uint64(0x100000001B3) + as_u64(idx)))
     # 24 bits: exactly representable in fp32, and so is the product with 2^-24
     return ((z >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
 

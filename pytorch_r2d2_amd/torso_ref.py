@@ -31,8 +31,10 @@ from typing import Optional
 
 import numpy as np
 
-from .lstm_ref import (U, _compare, _compare_bf16, bf16_bits, bf16_round, bf16_val,  # noqa: F401
-                       check_ownership, check_untouched, split_planes)
+from .lstm_ref import U
+# the ownership checks are not used below: they stay part of this oracle's interface
+from .refnum import (bf16_bits, bf16_round, bf16_val, check_ownership, check_untouched,  # noqa: F401
+                     compare, compare_bf16, split_planes)
 
 C = 32                      # channels of every conv layer
 EPS_BF16 = 2.0 ** -8        # bf16 unit roundoff: 8 significand bits, so half an ulp is up to 2^-8 |x|
@@ -261,7 +263,7 @@ def layer_reference(cols, wpk, b, scale: float):
         |x - (S scale + b)| <= (K + 2) u (T scale + |b|),
     the project's (n + 2) u sum|a||w| convention with the bias as one more term.  ReLU is
     1-Lipschitz, so the same bound holds for max(x, 0) against max(ref, 0) with no exclusion near
-    zero, and the stored value is the bf16 rounding of that (compared in the _compare_bf16 sense)."""
+    zero, and the stored value is the bf16 rounding of that (compared in the compare_bf16 sense)."""
     K = cols.shape[-1]
     a, w = cols.astype(np.float64), wpk.astype(np.float64)
     pre = a @ w.T * scale + b.astype(np.float64)
@@ -305,7 +307,7 @@ def check_forward(label, geo: Geo, frames, wts, stored, stride: int = 1, mutatio
     ref = forward_reference(geo, frames, wts, stored, stride, mutation)
     names = dict(save1=("frame", "pixel", "channel"), save2=("frame", "pixel", "channel"),
                  out=("frame", "channel", "pixel"))
-    return {k: _compare_bf16(label, k, np.asarray(stored[k]).reshape(r.shape), r, e, names[k])
+    return {k: compare_bf16(label, k, np.asarray(stored[k]).reshape(r.shape), r, e, names[k])
             for k, (r, e) in ref.items()}
 
 
@@ -455,8 +457,8 @@ def check_forward_sp(label, geo: Geo, frames, wts, stored, stride: int = 1, muta
     for k, (r, e) in ref.items():
         hi_bits = np.asarray(stored[k]).reshape(r.shape)
         hi = bf16_val(hi_bits).astype(np.float64)
-        uses[k] = max(_compare_bf16(label, k, hi_bits, r, e, names[k]),
-                      _compare_bf16(label, k + "_lo", np.asarray(stored[k + "_lo"]).reshape(r.shape), r - hi, e, names[k]))
+        uses[k] = max(compare_bf16(label, k, hi_bits, r, e, names[k]),
+                      compare_bf16(label, k + "_lo", np.asarray(stored[k + "_lo"]).reshape(r.shape), r - hi, e, names[k]))
     return uses
 
 
@@ -677,7 +679,7 @@ def slab_reference(geo: Geo, ops, grid: int, mutation: Optional[str] = None, sp:
 
 def check_slab(label, geo: Geo, ops, grid: int, slab, mutation=None, sp: bool = False) -> float:
     ref, bound = slab_reference(geo, ops, grid, mutation, sp)
-    return _compare(label, "slab", np.asarray(slab).reshape(ref.shape), ref, bound, ("row", "element"))
+    return compare(label, "slab", np.asarray(slab).reshape(ref.shape), ref, bound, ("row", "element"))
 
 
 def check_reduce(label, slab, dst, scale, grad, mutation=None) -> float:
@@ -687,7 +689,7 @@ def check_reduce(label, slab, dst, scale, grad, mutation=None) -> float:
     sc = np.ones_like(scale, np.float64) if mutation == "no_255" else np.where(scale == 1.0, 1.0, 1.0 / 255.0)
     ref = slab.sum(0) * sc
     bound = (slab.shape[0] + 2) * U * np.abs(slab).sum(0) * sc
-    return _compare(label, "grad", np.asarray(grad)[dst], ref, bound, ("element",))
+    return compare(label, "grad", np.asarray(grad)[dst], ref, bound, ("element",))
 
 
 def emulate_backward(geo: Geo, ops, grid: int) -> np.ndarray:

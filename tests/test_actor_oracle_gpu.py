@@ -13,64 +13,34 @@ kernels.
 With R2D2_ACTOR_ORACLE_REPORT=<file> the measured figures are written there
 (profiles/actor_oracle_errors.txt)."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from gpu_support import (DEV, Buf, LogEnv, Tree, buf_from_host, np_copy, packed_weights, qnet64,
+                         report_fixture, word)
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
 from pytorch_r2d2_amd import actor_ref as ar
 from pytorch_r2d2_amd import replay_ref as rr
-from pytorch_r2d2_amd.actor_batched import ActArgs, BatchedActor, PackedWeights
+from pytorch_r2d2_amd.actor_batched import ActArgs, BatchedActor
 from pytorch_r2d2_amd.config import get_config
-from pytorch_r2d2_amd.engine.layout import ParamLayout
 from pytorch_r2d2_amd.engine.replay_hbm import HBMReplay
 from pytorch_r2d2_amd.envs.synthetic import VecSyntheticAtari
-from pytorch_r2d2_amd.models import QNet
 from pytorch_r2d2_amd.ops._lib import kernels, stream_handle
 from test_actor_ref_cpu import CASES, check_steps, initial_flags, oracle, poison_init
-from test_replay_oracle_gpu import DEV, Buf, Tree, _word
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 MAX_DIRTY = 512
 PEND_SLACK = 32          # poisoned elements behind a pending list's capacity
-_REPORT = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    path = os.environ.get("R2D2_ACTOR_ORACLE_REPORT")
-    if path and _REPORT:
-        with open(path, "w") as f:
-            f.write("# actor.hip and BatchedActor._infer against actor_ref.py, one line per case\n"
-                    "# reward / priority / leaf : largest use of the oracle's bound (1.0 = at the bound);\n"
-                    "#          floor : largest share of the fp32 floor in a row's priority bound\n"
-                    "# infer  : largest error against float64 QNet / (2 x the error of the bf16-rounded\n"
-                    "#          float64 QNet), per output, and that error itself\n")
-            for line in _REPORT:
-                f.write(line + "\n")
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_gpu_error():
-    """A launch that faulted leaves the device in an error state: nothing more is launched."""
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"GPU error, no further launches: {e}", returncode=3)
-
-
-def _buf(a):
-    """A guarded device buffer that starts as the host array ``a`` (guards: the dtype's poison)."""
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint16:        # bf16 bit patterns
-        return Buf(torch.from_numpy(a.view(np.int16).reshape(-1)).view(torch.bfloat16), NAN)
-    poison = NAN if a.dtype.kind == "f" else (0xAB if a.dtype == np.uint8 else -1)
-    return Buf(a.reshape(-1), poison)
+_REPORT, _report = report_fixture(
+    "R2D2_ACTOR_ORACLE_REPORT",
+    "# actor.hip and BatchedActor._infer against actor_ref.py, one line per case\n"
+    "# reward / priority / leaf : largest use of the oracle's bound (1.0 = at the bound);\n"
+    "#          floor : largest share of the fp32 floor in a row's priority bound\n"
+    "# infer  : largest error against float64 QNet / (2 x the error of the bf16-rounded\n"
+    "#          float64 QNet), per output, and that error itself\n")
 
 
 def _host(buf, like):
@@ -88,18 +58,18 @@ class Launches:
         self.c, self.sp, self.lg = c, c["spec"], c["logs"]
         sp = self.sp
         self.init = poison_init(c)
-        self.b = {k: _buf(self.init[k]) for k in self.OUT}
+        self.b = {k: buf_from_host(self.init[k]) for k in self.OUT}
         fl, lv, _ = initial_flags(c)
         self.tree = Tree(lv.astype(np.float32))
         self.b["dirty"] = Buf.poisoned(MAX_DIRTY, torch.int32, -1)
-        self.dcount = _word(0)
+        self.dcount = word(0)
         z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=DEV)   # noqa: E731
         E, A, H = sp.E, sp.A, sp.H
         self.i = dict(obs=z(E, sp.FB, dt=torch.uint8), q_on=z(E, A), q_tg=z(E, A), h_new=z(2, E, H),
                       c_new=z(2, E, H), reward=z(E), done=z(E, dt=torch.bool), finished=z(E),
                       eps=torch.from_numpy(np.asarray(self.lg.eps, np.float32)).to(DEV))
         self.pend = [Buf.poisoned(sp.pend_cap + PEND_SLACK, torch.int32, -1) for _ in range(2)]
-        self.pend_cnt = [_word(0), _word(0)]
+        self.pend_cnt = [word(0), word(0)]
         self.S = 0
 
     def args(self, parity=0, **over):
@@ -258,26 +228,6 @@ def test_actor_launches_refuse_bad_arguments(name):
 
 
 # ================================================================== through the class
-class LogEnv(VecSyntheticAtari):
-    """The env's outputs stay in its persistent buffers until the next step."""
-
-    def outputs(self):
-        return (self._reward.cpu().numpy().copy(), self._done.cpu().numpy().copy(),
-                self._finished.cpu().numpy().copy())
-
-
-def _weights(cfg, seed):
-    torch.manual_seed(seed)
-    net = QNet("cpu", cfg.model, cfg.env)
-    w = PackedWeights(ParamLayout(cfg.model, cfg.env), DEV)
-    w.load(net.state_dict())
-    return net, w
-
-
-def _np(t):
-    return t.detach().cpu().numpy().copy()
-
-
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
 def test_batched_actor_replay_against_the_oracle(graph):
     """150 steps of a BatchedActor (E 8, sub-rings of 60 rows): the host's choice of the wrap
@@ -287,8 +237,8 @@ def test_batched_actor_replay_against_the_oracle(graph):
     cfg = get_config("atari57", **{"replay.burn_in": 4, "replay.learn": 6, "replay.overlap": 5,
                                    "replay.n_step": 3})
     rp = HBMReplay(cfg, DEV, capacity=E * cap_e, n_subrings=E)
-    _, won = _weights(cfg, 0)
-    _, wtg = _weights(cfg, 1)
+    _, won = packed_weights(cfg, 0)
+    _, wtg = packed_weights(cfg, 1)
     env = LogEnv(E, DEV, seed=3, episode_len=37, randomize_start=True)
     actor = BatchedActor(cfg, rp, env, won, wtg, seed=1)
     rc, lc = cfg.replay, cfg.learner
@@ -302,45 +252,45 @@ def test_batched_actor_replay_against_the_oracle(graph):
                 h_step=actor.h_step, ep_start=actor.ep_start, t=actor.t_d, head=actor.head_d,
                 act=actor.act, ret_ring=actor.ret_ring[: actor.R], ret_env=actor.ret_env[: actor.R],
                 ret_cnt=actor.ret_cnt)
-    init = {k: _np(v) for k, v in cols.items()}
-    init["marks"] = _np(actor.marks).reshape(actor.n + 2, E)
+    init = {k: np_copy(v) for k, v in cols.items()}
+    init["marks"] = np_copy(actor.marks).reshape(actor.n + 2, E)
     if graph:
         assert actor.can_capture
         actor.capture(warmup=0)
     log = {k: [] for k in ("obs", "q_on", "q_tg", "h_new", "c_new", "reward", "done", "finished", "act")}
     for _ in range(N):
-        log["obs"].append(_np(env.frames))
+        log["obs"].append(np_copy(env.frames))
         actor.step()
-        log["q_on"].append(_np(actor.infer.q["on"]))
-        log["q_tg"].append(_np(actor.infer.q["tg"]))
-        log["h_new"].append(np.stack([_np(actor.infer.h32_new[k]) for k in ("on", "tg")]))
-        log["c_new"].append(np.stack([_np(actor.infer.c_new[k]) for k in ("on", "tg")]))
+        log["q_on"].append(np_copy(actor.infer.q["on"]))
+        log["q_tg"].append(np_copy(actor.infer.q["tg"]))
+        log["h_new"].append(np.stack([np_copy(actor.infer.h32_new[k]) for k in ("on", "tg")]))
+        log["c_new"].append(np.stack([np_copy(actor.infer.c_new[k]) for k in ("on", "tg")]))
         r, d, f = env.outputs()
         log["reward"].append(r)
         log["done"].append(d)
         log["finished"].append(f)
-        log["act"].append(_np(actor.act))
+        log["act"].append(np_copy(actor.act))
     torch.cuda.synchronize()
     lg = ar.ActorLogs(**{k: np.stack(log[k]) for k in ar.ActorLogs._fields if k in log},
-                      eps=_np(actor.eps), seed=actor.seed)
+                      eps=np_copy(actor.eps), seed=actor.seed)
     ref = ar.ActorRef(sp, lg)
     assert np.array_equal(ref.act, np.stack(log["act"])), "chosen actions"
     want = ref.at(N)
     assert lg.done.sum() >= 2 * E and want["is_start"].sum() > E
-    got = {k: _np(v) for k, v in cols.items()}
-    got["h_valid"] = _np(actor.h_valid).astype(np.uint8)
-    got["marks"] = _np(actor.marks).reshape(actor.n + 2, E)
-    got["h32"] = np.stack([_np(actor.infer.h32[k]) for k in ("on", "tg")])
-    got["c"] = np.stack([_np(actor.infer.c[k]) for k in ("on", "tg")])
-    got["h_bf"] = np.stack([_np(actor.infer.h_bf[k].view(torch.int16)).view(np.uint16) for k in ("on", "tg")])
+    got = {k: np_copy(v) for k, v in cols.items()}
+    got["h_valid"] = np_copy(actor.h_valid).astype(np.uint8)
+    got["marks"] = np_copy(actor.marks).reshape(actor.n + 2, E)
+    got["h32"] = np.stack([np_copy(actor.infer.h32[k]) for k in ("on", "tg")])
+    got["c"] = np.stack([np_copy(actor.infer.c[k]) for k in ("on", "tg")])
+    got["h_bf"] = np.stack([np_copy(actor.infer.h_bf[k].view(torch.int16)).view(np.uint16) for k in ("on", "tg")])
     ar.check_exact(got, want, init)
     worst = dict(reward=ar.check_reward(got["reward"], want, sp, init["reward"]))
     worst.update(ar.check_priority(got["priority"], want, sp, init["priority"]))
-    leaves = _np(rp.tree[: rp.capacity])
+    leaves = np_copy(rp.tree[: rp.capacity])
     worst["leaf"] = ar.check_leaves(leaves, got["is_start"], got["priority"], want, sp)
-    rr.check_tree(_np(rp.tree), rp.tree_offs.tolist(), rp.tree_sizes.tolist(), leaves)
+    rr.check_tree(np_copy(rp.tree), rp.tree_offs.tolist(), rp.tree_sizes.tolist(), leaves)
     assert int(rp.dirty_count.item()) == 0
-    ar.check_dirty(_np(rp.dirty), want, sp.cap)
+    ar.check_dirty(np_copy(rp.dirty), want, sp.cap)
     rets = actor.finished_returns
     assert len(rets) == want["ret_cnt"] <= actor.R
     assert [np.float32(x) for x in rets] == [lg.finished[s, e] for s, e in ref.rets]
@@ -350,38 +300,6 @@ def test_batched_actor_replay_against_the_oracle(graph):
 
 
 # ================================================================== inference
-def _bf(x):
-    return x.float().bfloat16().double()
-
-
-def _qnet64(net, frames, h, c, rounded):
-    """Q, h', c' of one step of ``net`` in float64; ``rounded``: GEMM operands (conv / LSTM / first
-    head layer weights, the activations entering them) and the carried h rounded to bf16 where the
-    kernels round them (1 / 255 and every bias applied to the wide accumulator)."""
-    sd = {k: v.double() for k, v in net.state_dict().items()}
-    w = (lambda k: _bf(sd[k])) if rounded else (lambda k: sd[k])
-    r = _bf if rounded else (lambda x: x)
-    F = torch.nn.functional
-    x = frames.double().view(-1, *net.in_shape)
-    a = r(torch.relu(F.conv2d(x, w("vis_layers.0.weight"), None, stride=4) / 255.0
-                     + sd["vis_layers.0.bias"][None, :, None, None]))
-    a = r(torch.relu(F.conv2d(a, w("vis_layers.2.weight"), sd["vis_layers.2.bias"], stride=2)))
-    a = r(torch.relu(F.conv2d(a, w("vis_layers.4.weight"), sd["vis_layers.4.bias"], stride=1)))
-    feat = a.reshape(a.shape[0], -1)
-    bias = (net.lstm.bias_ih.detach() + net.lstm.bias_hh.detach()).double() if rounded else \
-        sd["lstm.bias_ih"] + sd["lstm.bias_hh"]
-    gates = feat @ w("lstm.weight_ih").t() + bias + r(h.double()) @ w("lstm.weight_hh").t()
-    i, f, g, o = gates.chunk(4, dim=1)
-    c2 = torch.sigmoid(f) * c.double() + torch.sigmoid(i) * torch.tanh(g)
-    h2 = torch.sigmoid(o) * torch.tanh(c2)
-    hin = r(h2)
-    zv = r(hin @ w("val.0.weight").t())          # the first head layer is stored before its bias
-    za = r(hin @ w("adv.0.weight").t())
-    v = torch.relu(zv + sd["val.0.bias"]) @ sd["val.2.weight"].t() + sd["val.2.bias"]
-    adv = torch.relu(za + sd["adv.0.bias"]) @ sd["adv.2.weight"].t() + sd["adv.2.bias"]
-    return v + adv - adv.mean(dim=1, keepdim=True), h2, c2
-
-
 def test_actor_inference_against_float64_qnet():
     """BatchedActor._infer (fused torso, bf16 x-projection, one LSTM step, head GEMM, dueling
     epilogue) on the Atari geometry, E = 5, six steps with carried state and a reset of every env
@@ -393,7 +311,7 @@ def test_actor_inference_against_float64_qnet():
     cfg = get_config("atari57", **{"replay.burn_in": 4, "replay.learn": 6, "replay.overlap": 5,
                                    "replay.n_step": 3})
     rp = HBMReplay(cfg, DEV, capacity=E * 40, n_subrings=E)
-    nets = dict(zip(("on", "tg"), (_weights(cfg, 0), _weights(cfg, 1))))
+    nets = dict(zip(("on", "tg"), (packed_weights(cfg, 0), packed_weights(cfg, 1))))
     env = VecSyntheticAtari(E, DEV, seed=4, episode_len=3, randomize_start=False)
     actor = BatchedActor(cfg, rp, env, nets["on"][1], nets["tg"][1], seed=2)
     assert actor.infer.fused_torso
@@ -409,8 +327,8 @@ def test_actor_inference_against_float64_qnet():
         torch.cuda.synchronize()
         for k, (net, _) in nets.items():
             h, c = carried[k]
-            exact = _qnet64(net, frames, h, c, False)
-            emu = _qnet64(net, frames, h, c, True)
+            exact = qnet64(net, frames, h, c, False)
+            emu = qnet64(net, frames, h, c, True)
             got = (actor.infer.q[k], actor.infer.h32_new[k], actor.infer.c_new[k])
             bound_q = None
             for nm, g, x, m in zip(("q", "h", "c"), got, exact, emu):

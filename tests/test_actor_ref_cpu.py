@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from pytorch_r2d2_amd import actor_ref as ar
+from pytorch_r2d2_amd import refnum as rn
 from pytorch_r2d2_amd import replay_ref as rr
 from pytorch_r2d2_amd import td_ref
 
@@ -481,7 +482,7 @@ def test_checks_reject_a_mutated_oracle(mutation):
 def test_bf16_rounding_and_uniform_draws():
     x = np.asarray([1.0, 1.00390625, 1.01171875, -3.1415927, 1e-20, 0.0], f32)
     # 1 + 2^-8 ties to even (down), 1 + 3 * 2^-8 ties to even (up)
-    assert ar.bf16_bits(x)[:3].tolist() == [0x3F80, 0x3F80, 0x3F82]
+    assert rn.bf16_bits(x)[:3].tolist() == [0x3F80, 0x3F80, 0x3F82]
     import torch
     t = torch.from_numpy(np.random.default_rng(0).standard_normal(4096).astype(f32))
-    assert np.array_equal(ar.bf16_bits(t.numpy()), t.bfloat16().view(torch.int16).numpy().view(np.uint16))
+    assert np.array_equal(rn.bf16_bits(t.numpy()), t.bfloat16().view(torch.int16).numpy().view(np.uint16))

@@ -13,60 +13,30 @@ the CPU that the oracle's check rejects wrong kernels.
 With R2D2_EVAL_ORACLE_REPORT=<file> the measured inference errors are written there
 (profiles/eval_oracle_errors.txt)."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from gpu_support import (DEV, buf_from_host, engine_state, packed_weights, pong_small, qnet64,
+                         report_fixture, train_with_evals, word)
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
 from pytorch_r2d2_amd import eval_ref as er
-from pytorch_r2d2_amd.actor_batched import PackedWeights, engine_weights
 from pytorch_r2d2_amd.config import get_config
-from pytorch_r2d2_amd.engine.layout import ParamLayout
 from pytorch_r2d2_amd.envs.synthetic import VecSyntheticAtari
 from pytorch_r2d2_amd.evaluator import BatchedEvaluator, EvalArgs, make_eval_env
 from pytorch_r2d2_amd.models import QNet
 from pytorch_r2d2_amd.ops._lib import kernels, stream_handle
 from pytorch_r2d2_amd.utils.metrics import read_jsonl
-from test_actor_oracle_gpu import _qnet64
 from test_eval_ref_cpu import E, EPS, H, K, LOGS, N, SIZES, poison_init
-from test_hoist_gpu import _state as _engine_state
-from test_replay_oracle_gpu import DEV, Buf, _word
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-_REPORT = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    path = os.environ.get("R2D2_EVAL_ORACLE_REPORT")
-    if path and _REPORT:
-        with open(path, "w") as f:
-            f.write("# BatchedEvaluator inference (one net of infer.PolicyInference) against float64 QNet\n"
-                    "# per output: largest error / (2 x the error of the bf16-rounded float64 QNet),\n"
-                    "#             and that error itself (1.0 = at the bound)\n")
-            for line in _REPORT:
-                f.write(line + "\n")
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_gpu_error():
-    """A launch that faulted leaves the device in an error state: nothing more is launched."""
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"GPU error, no further launches: {e}", returncode=3)
-
-
-def _buf(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint16:        # bf16 bit patterns
-        return Buf(torch.from_numpy(a.view(np.int16).reshape(-1)).view(torch.bfloat16), NAN)
-    return Buf(a.reshape(-1), NAN if a.dtype.kind == "f" else -1)
+_REPORT, _report = report_fixture(
+    "R2D2_EVAL_ORACLE_REPORT",
+    "# BatchedEvaluator inference (one net of infer.PolicyInference) against float64 QNet\n"
+    "# per output: largest error / (2 x the error of the bf16-rounded float64 QNet),\n"
+    "#             and that error itself (1.0 = at the bound)\n")
 
 
 # ================================================================== 1. / 2. the launches
@@ -76,8 +46,8 @@ class Launches:
     def __init__(self, A):
         self.A, self.lg = A, LOGS[A]
         self.init = poison_init()
-        self.b = {k: _buf(self.init[k]) for k in self.OUT}
-        self.ticket = _word(0)
+        self.b = {k: buf_from_host(self.init[k]) for k in self.OUT}
+        self.ticket = word(0)
         z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=DEV)   # noqa: E731
         self.i = dict(q=z(E, A), h_new=z(E, H), c_new=z(E, H), done=z(E, dt=torch.bool), finished=z(E),
                       eps=torch.from_numpy(EPS).to(DEV))
@@ -161,14 +131,6 @@ def test_eval_launches_refuse_bad_arguments():
 
 
 # ================================================================== 3. inference
-def _weights(cfg, seed):
-    torch.manual_seed(seed)
-    net = QNet("cpu", cfg.model, cfg.env)
-    w = PackedWeights(ParamLayout(cfg.model, cfg.env), DEV)
-    w.load(net.state_dict())
-    return net, w
-
-
 def test_evaluator_inference_against_float64_qnet():
     """The evaluator's one-net inference on the Atari geometry, E = 5, six steps with carried state
     and a reset of every env after the third (episode_len 3).  The bound is the actor test's
@@ -177,7 +139,7 @@ def test_evaluator_inference_against_float64_qnet():
     the evaluator's own Q and the float64 one wherever the float64 top-two gap exceeds the bound."""
     n = 5
     cfg = get_config("atari57")
-    net, w = _weights(cfg, 0)
+    net, w = packed_weights(cfg, 0)
     env = VecSyntheticAtari(n, DEV, seed=4, episode_len=3, randomize_start=False)
     ev = BatchedEvaluator(cfg, env, w, episodes_per_env=2, seed=2)
     assert ev.infer.fused_torso
@@ -191,8 +153,8 @@ def test_evaluator_inference_against_float64_qnet():
             assert h.any()
         ev.step()
         torch.cuda.synchronize()
-        exact = _qnet64(net, frames, h, c, False)
-        emu = _qnet64(net, frames, h, c, True)
+        exact = qnet64(net, frames, h, c, False)
+        emu = qnet64(net, frames, h, c, True)
         got = (ev.infer.q["on"], ev.infer.h32_new["on"], ev.infer.c_new["on"])
         bound_q = None
         for nm, g, x, m in zip(("q", "h", "c"), got, exact, emu):
@@ -215,7 +177,7 @@ def test_evaluator_inference_against_float64_qnet():
 
 # ================================================================== 4. end to end
 def _evaluator(cfg, n, k, seed=11, **kw):
-    _, w = _weights(cfg, 5)
+    _, w = packed_weights(cfg, 5)
     env = make_eval_env(cfg, DEV, n, seed=seed)
     return BatchedEvaluator(cfg, env, w, episodes_per_env=k, seed=seed, **kw)
 
@@ -259,7 +221,7 @@ def test_evaluation_end_to_end(preset):
     assert (part["lengths"][:, 0] == L).all() and (part["lengths"][:, 1] == -1).all()
     # a second run restarts the envs (new episodes) and refills the tables; other weights drop the graph
     assert short.run()["complete"] and short.steps == 16
-    short.set_weights(_weights(cfg, 6)[1])
+    short.set_weights(packed_weights(cfg, 6)[1])
     assert short.graph is None and short.run()["complete"]
 
 
@@ -277,38 +239,13 @@ def test_epsilon_one_acts_at_random_and_zero_never_does():
 
 
 # ================================================================== 5. training is untouched
-def _train(evaluate):
-    from pytorch_r2d2_amd.engine.learner_engine import LearnerEngine
-    from pytorch_r2d2_amd.engine.replay_hbm import HBMReplay
-    cfg = get_config("atari57", **{"learner.batch_size": 4, "replay.capacity": 8192, "replay.n_subrings": 4,
-                                   "replay.burn_in": 4, "replay.learn": 4, "replay.overlap": 4,
-                                   "learner.use_graph": False, "env.episode_len": 8})
-    torch.manual_seed(0)
-    rp = HBMReplay(cfg, torch.device(DEV, 0))
-    rp.fill_synthetic(episode_len=64, seed=0)
-    eng = LearnerEngine(cfg, rp, torch.device(DEV, 0))
-    ev = None
-    if evaluate:
-        ev = BatchedEvaluator(cfg, make_eval_env(cfg, DEV, 4), engine_weights(eng)[0], episodes_per_env=1)
-    means = []
-    for _ in range(6):
-        eng.step()
-        if ev is not None:
-            res = ev.run()
-            assert res["complete"] and res["episodes"] == 4
-            means.append(res["mean_return"])
-    torch.cuda.synchronize()
-    assert eng.error_word() == 0
-    return rp, eng, means
-
-
 def test_training_is_untouched_by_evaluations():
     """The engine of smoke() (batch 4, burn-in 4, learn 4, 4 sub-rings, fill_synthetic), 6 learner
     steps, once with an evaluation of the live weights after every step: master weights, optimizer
     moments, packed weights, priorities and the tree are bit-equal, and so are the replay's write
     count and the number of steps that kept their pre-sampled batch."""
-    a, b = _train(False), _train(True)
-    sa, sb = _engine_state(a[0], a[1]), _engine_state(b[0], b[1])
+    a, b = train_with_evals(False), train_with_evals(True)
+    sa, sb = engine_state(a[0], a[1]), engine_state(b[0], b[1])
     sa.update(is_start=a[0].is_start, n_valid=a[0].n_valid)
     sb.update(is_start=b[0].is_start, n_valid=b[0].n_valid)
     bad = [k for k in sa if not torch.equal(sa[k], sb[k])]
@@ -319,17 +256,9 @@ def test_training_is_untouched_by_evaluations():
 
 
 # ================================================================== 6. drivers
-def _pong_small(**over):
-    kw = {"replay.burn_in": 4, "replay.learn": 6, "replay.overlap": 5, "replay.n_step": 3,
-          "learner.batch_size": 8, "actor.envs_per_actor": 16, "env.episode_len": 12,
-          "eval.envs": 4, "eval.episodes_per_env": 2}
-    kw.update(over)
-    return get_config("pong", **kw)
-
-
 def test_run_native_evaluates_every_n_steps(tmp_path):
     from pytorch_r2d2_amd.runner import run_native
-    cfg = _pong_small()
+    cfg = pong_small()
     path = str(tmp_path / "m.jsonl")
     out = run_native(cfg, steps=4, eval_every=2, warmup_rows=16 * 40, capacity=16 * 128, log_every=2,
                      metrics_path=path)
@@ -349,7 +278,7 @@ def test_run_eval_and_main_on_a_reference_checkpoint(tmp_path):
     import main
     from pytorch_r2d2_amd.runner import run_eval
     from pytorch_r2d2_amd.utils.checkpoint import save_full_checkpoint, save_reference_checkpoint
-    cfg = _pong_small()
+    cfg = pong_small()
     torch.manual_seed(3)
     net = QNet("cpu", cfg.model, cfg.env)
     ckpt = save_reference_checkpoint(net.state_dict(), 7, str(tmp_path / "save"))

@@ -10,9 +10,9 @@ import torch
 
 from pytorch_r2d2_amd import eval_ref as er
 from pytorch_r2d2_amd import replay_ref as rr
-from pytorch_r2d2_amd.actor_ref import bf16_bits
 from pytorch_r2d2_amd.config import PRESETS, get_config
 from pytorch_r2d2_amd.evaluator import BatchedEvaluator, aggregate, check_eval_params
+from pytorch_r2d2_amd.refnum import bf16_bits
 
 E, H, K, N = 5, 8, 2, 12
 EPS = np.asarray([0.0, 1.0, 0.4, 0.0, 0.4], np.float32)

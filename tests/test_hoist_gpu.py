@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import engine_state
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 
@@ -22,18 +24,6 @@ def _engine(hoist, B=64, interval=3, graph=True, **kw):
     rp.fill_synthetic(episode_len=200, seed=3)
     eng = LearnerEngine(cfg, rp, DEV)
     return rp, eng
-
-
-def _state(rp, eng):
-    # the packed layouts by name (their alignment padding is never read and not compared)
-    out = {"master": eng.master, "target": eng.target, "opt_a": eng.opt_a, "opt_b": eng.opt_b,
-           "lstm_b": eng.lstm_b, "lstm_b_t": eng.lstm_b_t, "priority": rp.priority,
-           "tree": rp.tree, "step": rp.step, "loss": eng.loss}
-    for tag, (bf, f32) in {"": (eng.bf, eng.f32), "_t": (eng.bf_t, eng.f32_t)}.items():
-        for plane in range(bf.shape[0]):
-            for k, v in eng.layout.packed_views(bf[plane], f32).items():
-                out["%s%s.%d" % (k, tag, plane)] = v
-    return out
 
 
 @pytest.mark.parametrize("graph,B,early,hoist_first", [
@@ -72,7 +62,7 @@ def test_hoisted_step_is_bitwise_the_plain_step(graph, B, early, hoist_first):
         plain.step()
         hoist.step()
         torch.cuda.synchronize()
-        a, b = _state(rp0, plain), _state(rp1, hoist)
+        a, b = engine_state(rp0, plain), engine_state(rp1, hoist)
         bad = [k for k in a if not torch.equal(a[k], b[k])]
         assert not bad, (i, bad)
     assert plain.error_word() == 0 and hoist.error_word() == 0
@@ -153,7 +143,7 @@ def test_fused_pack_tail_matches_separate_pack(hoist):
         a.step()
         b.step()
         torch.cuda.synchronize()
-        sa, sb = _state(rp0, a), _state(rp1, b)
+        sa, sb = engine_state(rp0, a), engine_state(rp1, b)
         bad = [k for k in sa if not torch.equal(sa[k], sb[k])]
         assert not bad, (i, bad)
 
@@ -172,7 +162,7 @@ def test_folded_torso_reduce_matches_separate_launch(hoist):
         a.step()
         b.step()
         torch.cuda.synchronize()
-        sa, sb = _state(rp0, a), _state(rp1, b)
+        sa, sb = engine_state(rp0, a), engine_state(rp1, b)
         sa["grad"], sb["grad"] = a.grad, b.grad
         bad = [k for k in sa if not torch.equal(sa[k], sb[k])]
         assert not bad, (i, bad)
@@ -193,7 +183,7 @@ def test_chunked_graph_matches_step_loop():
             plain.step()
         ch.run_steps(n)
         torch.cuda.synchronize()
-        a, b = _state(rp0, plain), _state(rp1, ch)
+        a, b = engine_state(rp0, plain), engine_state(rp1, ch)
         bad = [k for k in a if not torch.equal(a[k], b[k])]
         assert not bad, (n, ch.steps_done, bad)
     assert ch.steps_done == plain.steps_done == 27
@@ -214,7 +204,7 @@ def test_hoisted_step_without_fused_td_forks_after_td():
         plain.step()
         hoist.step()
         torch.cuda.synchronize()
-        a, b = _state(rp0, plain), _state(rp1, hoist)
+        a, b = engine_state(rp0, plain), engine_state(rp1, hoist)
         bad = [k for k in a if not torch.equal(a[k], b[k])]
         assert not bad, (i, bad)
     assert plain.error_word() == 0 and hoist.error_word() == 0

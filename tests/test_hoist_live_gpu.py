@@ -12,8 +12,8 @@ the ring wraps several times in a run."""
 import pytest
 import torch
 
+from gpu_support import engine_state
 from pytorch_r2d2_amd.engine.replay_check import bootstrap_violations, check_windows, ring_offsets
-from test_hoist_gpu import _state as _engine_state
 from test_native_gpu import _record, _small_cfg, _tree_consistent
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +50,7 @@ def _live(hoist, graph=True, **over):
 
 
 def _state(rp, eng):
-    out = _engine_state(rp, eng)      # weights, moments, packs, priority, tree, step, loss
+    out = engine_state(rp, eng)      # weights, moments, packs, priority, tree, step, loss
     out.update(is_start=rp.is_start, n_valid=rp.n_valid, starts=eng.starts)
     return out
 

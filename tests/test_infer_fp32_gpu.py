@@ -12,52 +12,33 @@ The fp32 PyTorch term is computed on the CPU here, so the bound is measured on t
 With R2D2_INFER_FP32_REPORT=<file> the measured figures are written there
 (profiles/actor_fp32_oracle_errors.txt)."""
 import copy
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from gpu_support import (DEV, LogEnv, engine_state, np_copy, packed_weights, pong_small, qnet64,
+                         report_fixture, train_with_evals)
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
 from pytorch_r2d2_amd import actor_ref as ar
 from pytorch_r2d2_amd import eval_ref as er
 from pytorch_r2d2_amd import replay_ref as rr
-from pytorch_r2d2_amd.actor_batched import BatchedActor, PackedWeights, engine_weights
+from pytorch_r2d2_amd.actor_batched import BatchedActor
 from pytorch_r2d2_amd.config import get_config
-from pytorch_r2d2_amd.engine.layout import ParamLayout
 from pytorch_r2d2_amd.engine.replay_hbm import HBMReplay
 from pytorch_r2d2_amd.envs.synthetic import VecSyntheticAtari
-from pytorch_r2d2_amd.evaluator import BatchedEvaluator, make_eval_env
+from pytorch_r2d2_amd.evaluator import BatchedEvaluator
 from pytorch_r2d2_amd.models import QNet
 from pytorch_r2d2_amd.utils.metrics import read_jsonl
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 REL_FLOOR = 2e-5
-_REPORT = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    path = os.environ.get("R2D2_INFER_FP32_REPORT")
-    if path and _REPORT:
-        with open(path, "w") as f:
-            f.write("# fp32 (split-precision) inference against float64 QNet, one line per case\n"
-                    "# per output: largest error / bound, the largest error itself, and the bf16-operand\n"
-                    "#             emulation's largest error on the same inputs [in brackets]\n"
-                    "# bound = max(2 x |fp32 PyTorch QNet - float64|, 2e-5 x max|float64|)  (1.0 = at the bound)\n")
-            for line in _REPORT:
-                f.write(line + "\n")
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_gpu_error():
-    """A launch that faulted leaves the device in an error state: nothing more is launched."""
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"GPU error, no further launches: {e}", returncode=3)
+_REPORT, _report = report_fixture(
+    "R2D2_INFER_FP32_REPORT",
+    "# fp32 (split-precision) inference against float64 QNet, one line per case\n"
+    "# per output: largest error / bound, the largest error itself, and the bf16-operand\n"
+    "#             emulation's largest error on the same inputs [in brackets]\n"
+    "# bound = max(2 x |fp32 PyTorch QNet - float64|, 2e-5 x max|float64|)  (1.0 = at the bound)\n")
 
 
 @pytest.fixture(autouse=True)
@@ -73,47 +54,6 @@ def _restore_device_facts():
 
 
 SMALL = {"replay.burn_in": 4, "replay.learn": 6, "replay.overlap": 5, "replay.n_step": 3}
-
-
-def _weights(cfg, seed, split=True):
-    torch.manual_seed(seed)
-    net = QNet("cpu", cfg.model, cfg.env)
-    w = PackedWeights(ParamLayout(cfg.model, cfg.env), DEV, split=split)
-    w.load(net.state_dict())
-    return net, w
-
-
-def _np(t):
-    return t.detach().cpu().numpy().copy()
-
-
-def _bf(x):
-    return x.float().bfloat16().double()
-
-
-def _qnet64_bf16(net, frames, h, c):
-    """Q, h', c' of one step of ``net`` in float64 with the GEMM operands (conv / LSTM / first head
-    layer weights, the activations entering them) and the carried h rounded to bf16 where the bf16
-    kernels round them: the emulation of the bf16 inference path."""
-    sd = {k: v.double() for k, v in net.state_dict().items()}
-    w = lambda k: _bf(sd[k])  # noqa: E731
-    F = torch.nn.functional
-    x = frames.double().view(-1, *net.in_shape)
-    a = _bf(torch.relu(F.conv2d(x, w("vis_layers.0.weight"), None, stride=4) / 255.0
-                       + sd["vis_layers.0.bias"][None, :, None, None]))
-    a = _bf(torch.relu(F.conv2d(a, w("vis_layers.2.weight"), sd["vis_layers.2.bias"], stride=2)))
-    a = _bf(torch.relu(F.conv2d(a, w("vis_layers.4.weight"), sd["vis_layers.4.bias"], stride=1)))
-    feat = a.reshape(a.shape[0], -1)
-    bias = (net.lstm.bias_ih.detach() + net.lstm.bias_hh.detach()).double()
-    gates = feat @ w("lstm.weight_ih").t() + bias + _bf(h.double()) @ w("lstm.weight_hh").t()
-    i, f, g, o = gates.chunk(4, dim=1)
-    c2 = torch.sigmoid(f) * c.double() + torch.sigmoid(i) * torch.tanh(g)
-    h2 = torch.sigmoid(o) * torch.tanh(c2)
-    hin = _bf(h2)
-    zv, za = _bf(hin @ w("val.0.weight").t()), _bf(hin @ w("adv.0.weight").t())
-    v = torch.relu(zv + sd["val.0.bias"]) @ sd["val.2.weight"].t() + sd["val.2.bias"]
-    adv = torch.relu(za + sd["adv.0.bias"]) @ sd["adv.2.weight"].t() + sd["adv.2.bias"]
-    return v + adv - adv.mean(dim=1, keepdim=True), h2, c2
 
 
 class Refs:
@@ -132,7 +72,7 @@ class Refs:
         exact = (q[0], hs[0], cs[0])
         q, hs, cs = self.net32.seq_forward(x.float() / 255.0, h.float(), c.float())
         f32 = (q[0].double(), hs[0].double(), cs[0].double())
-        emu = _qnet64_bf16(self.net32, frames, h, c)
+        emu = qnet64(self.net32, frames, h, c, rounded=True)
         bound = [max(2.0 * float((a - x_).abs().max()), REL_FLOOR * float(x_.abs().max()))
                  for a, x_ in zip(f32, exact)]
         return exact, bound, [float((m - x_).abs().max()) for m, x_ in zip(emu, exact)]
@@ -167,7 +107,7 @@ def test_actor_fp32_inference_against_float64_qnet(E):
     (episode_len 3).  E = 130 runs the LSTM step as two row halves of 65 per net."""
     cfg = get_config("atari57", **SMALL, **{"actor.compute_dtype": "fp32"})
     rp = HBMReplay(cfg, DEV, capacity=E * 40, n_subrings=E)
-    nets = dict(zip(("on", "tg"), (_weights(cfg, 0), _weights(cfg, 1))))
+    nets = dict(zip(("on", "tg"), (packed_weights(cfg, 0, split=True), packed_weights(cfg, 1, split=True))))
     refs = {k: Refs(net) for k, (net, _) in nets.items()}
     env = VecSyntheticAtari(E, DEV, seed=4, episode_len=3, randomize_start=False)
     actor = BatchedActor(cfg, rp, env, nets["on"][1], nets["tg"][1], seed=2)
@@ -195,8 +135,8 @@ def test_actor_fp32_inference_against_float64_qnet(E):
 
 def _actor(cfg, E, cap_e, seed_env=3, env_cls=VecSyntheticAtari):
     rp = HBMReplay(cfg, DEV, capacity=E * cap_e, n_subrings=E)
-    _, won = _weights(cfg, 0)
-    _, wtg = _weights(cfg, 1)
+    _, won = packed_weights(cfg, 0, split=True)
+    _, wtg = packed_weights(cfg, 1, split=True)
     env = env_cls(E, DEV, seed=seed_env, episode_len=37, randomize_start=True)
     return rp, env, BatchedActor(cfg, rp, env, won, wtg, seed=1)
 
@@ -230,13 +170,6 @@ def test_captured_fp32_step_replays_bit_for_bit():
     assert outs[0]["hs_cs"].any() and outs[0]["priority"].any()
 
 
-class LogEnv(VecSyntheticAtari):
-    """The env's outputs stay in its persistent buffers until the next step."""
-
-    def outputs(self):
-        return _np(self._reward), _np(self._done), _np(self._finished)
-
-
 def test_fp32_actor_replay_rows_against_the_oracle():
     """150 steps of an fp32 BatchedActor (E 8, sub-rings of 60 rows): the stored states of the
     first 40 rows are bit for bit the carried fp32 (h32, c), and every column passes the class-level
@@ -257,51 +190,51 @@ def test_fp32_actor_replay_rows_against_the_oracle():
                 h_step=actor.h_step, ep_start=actor.ep_start, t=actor.t_d, head=actor.head_d,
                 act=actor.act, ret_ring=actor.ret_ring[: actor.R], ret_env=actor.ret_env[: actor.R],
                 ret_cnt=actor.ret_cnt)
-    init = {k: _np(v) for k, v in cols.items()}
-    init["marks"] = _np(actor.marks).reshape(actor.n + 2, E)
+    init = {k: np_copy(v) for k, v in cols.items()}
+    init["marks"] = np_copy(actor.marks).reshape(actor.n + 2, E)
     log = {k: [] for k in ("obs", "q_on", "q_tg", "h_new", "c_new", "reward", "done", "finished", "act")}
     carried = []
     for s in range(N):
-        log["obs"].append(_np(env.frames))
+        log["obs"].append(np_copy(env.frames))
         if s < 40:
-            carried.append(np.stack([np.concatenate([_np(actor.infer.h32[k]), _np(actor.infer.c[k])], axis=1)
+            carried.append(np.stack([np.concatenate([np_copy(actor.infer.h32[k]), np_copy(actor.infer.c[k])], axis=1)
                                      for k in ("on", "tg")]))
         actor.step()
-        log["q_on"].append(_np(actor.infer.q["on"]))
-        log["q_tg"].append(_np(actor.infer.q["tg"]))
-        log["h_new"].append(np.stack([_np(actor.infer.h32_new[k]) for k in ("on", "tg")]))
-        log["c_new"].append(np.stack([_np(actor.infer.c_new[k]) for k in ("on", "tg")]))
+        log["q_on"].append(np_copy(actor.infer.q["on"]))
+        log["q_tg"].append(np_copy(actor.infer.q["tg"]))
+        log["h_new"].append(np.stack([np_copy(actor.infer.h32_new[k]) for k in ("on", "tg")]))
+        log["c_new"].append(np.stack([np_copy(actor.infer.c_new[k]) for k in ("on", "tg")]))
         r, d, f = env.outputs()
         log["reward"].append(r)
         log["done"].append(d)
         log["finished"].append(f)
-        log["act"].append(_np(actor.act))
+        log["act"].append(np_copy(actor.act))
         if s == 39:     # rows 0 .. 39 of every sub-ring, before the ring wraps
             want = np.stack(carried)                                  # (40, 2, E, 2H)
             for i, col in enumerate((rp.hs_cs, rp.target_hs_cs)):
-                got = _np(col).reshape(E, cap_e, -1)[:, :40].transpose(1, 0, 2)
+                got = np_copy(col).reshape(E, cap_e, -1)[:, :40].transpose(1, 0, 2)
                 assert np.array_equal(got.view(np.uint32), want[:, i].view(np.uint32)), \
                     "stored states are not the carried fp32 states"
             assert want[1:].any()
     torch.cuda.synchronize()
     lg = ar.ActorLogs(**{k: np.stack(log[k]) for k in ar.ActorLogs._fields if k in log},
-                      eps=_np(actor.eps), seed=actor.seed)
+                      eps=np_copy(actor.eps), seed=actor.seed)
     ref = ar.ActorRef(sp, lg)
     assert np.array_equal(ref.act, np.stack(log["act"])), "chosen actions"
     want = ref.at(N)
     assert lg.done.sum() >= 2 * E and want["is_start"].sum() > E
-    got = {k: _np(v) for k, v in cols.items()}
-    got["h_valid"] = _np(actor.h_valid).astype(np.uint8)
-    got["marks"] = _np(actor.marks).reshape(actor.n + 2, E)
-    got["h32"] = np.stack([_np(actor.infer.h32[k]) for k in ("on", "tg")])
-    got["c"] = np.stack([_np(actor.infer.c[k]) for k in ("on", "tg")])
-    got["h_bf"] = np.stack([_np(actor.infer.h_bf[k].view(torch.int16)).view(np.uint16) for k in ("on", "tg")])
+    got = {k: np_copy(v) for k, v in cols.items()}
+    got["h_valid"] = np_copy(actor.h_valid).astype(np.uint8)
+    got["marks"] = np_copy(actor.marks).reshape(actor.n + 2, E)
+    got["h32"] = np.stack([np_copy(actor.infer.h32[k]) for k in ("on", "tg")])
+    got["c"] = np.stack([np_copy(actor.infer.c[k]) for k in ("on", "tg")])
+    got["h_bf"] = np.stack([np_copy(actor.infer.h_bf[k].view(torch.int16)).view(np.uint16) for k in ("on", "tg")])
     ar.check_exact(got, want, init)
     worst = dict(reward=ar.check_reward(got["reward"], want, sp, init["reward"]))
     worst.update(ar.check_priority(got["priority"], want, sp, init["priority"]))
-    leaves = _np(rp.tree[: rp.capacity])
+    leaves = np_copy(rp.tree[: rp.capacity])
     worst["leaf"] = ar.check_leaves(leaves, got["is_start"], got["priority"], want, sp)
-    rr.check_tree(_np(rp.tree), rp.tree_offs.tolist(), rp.tree_sizes.tolist(), leaves)
+    rr.check_tree(np_copy(rp.tree), rp.tree_offs.tolist(), rp.tree_sizes.tolist(), leaves)
     print("infer-fp32: class-level check", worst)
     assert worst["reward"] < 1.0 and worst["use"] < 1.0 and worst["leaf"] < 1.0
 
@@ -313,7 +246,7 @@ def test_fp32_evaluator_inference_and_bookkeeping():
     and env outputs."""
     n, K = 5, 2
     cfg = get_config("atari57", **{"eval.compute_dtype": "fp32"})
-    net, w = _weights(cfg, 0)
+    net, w = packed_weights(cfg, 0, split=True)
     ref = Refs(net)
     env = LogEnv(n, DEV, seed=4, episode_len=3, randomize_start=False)
     ev = BatchedEvaluator(cfg, env, w, episodes_per_env=K, seed=2)
@@ -339,32 +272,24 @@ def test_fp32_evaluator_inference_and_bookkeeping():
         assert torch.equal(act[clear], top.indices[:, 0][clear])
         _check_planes(ev.infer, "on")
         r, d, f = env.outputs()
-        for k, v in (("q", _np(ev.infer.q["on"])), ("h_new", _np(ev.infer.h32_new["on"])), ("c_new", _np(ev.infer.c_new["on"])),
+        for k, v in (("q", np_copy(ev.infer.q["on"])), ("h_new", np_copy(ev.infer.h32_new["on"])), ("c_new", np_copy(ev.infer.c_new["on"])),
                      ("reward", r), ("done", d), ("finished", f)):
             log[k].append(v)
-        lg = er.EvalLogs(**{k: np.stack(v) for k, v in log.items()}, eps=_np(ev.eps), seed=ev.seed)
-        got = dict(act=_np(ev.act), h32=_np(ev.infer.h32["on"]), c=_np(ev.infer.c["on"]),
-                   h_bf=_np(ev.infer.h_bf["on"].view(torch.int16)).view(np.uint16), ret=_np(ev.ret),
-                   ep_len=_np(ev.ep_len), n_done=_np(ev.n_done), len=_np(ev.len),
-                   total_done=_np(ev.total_done), counted_steps=_np(ev.counted_steps), t=_np(ev.t_d))
+        lg = er.EvalLogs(**{k: np.stack(v) for k, v in log.items()}, eps=np_copy(ev.eps), seed=ev.seed)
+        got = dict(act=np_copy(ev.act), h32=np_copy(ev.infer.h32["on"]), c=np_copy(ev.infer.c["on"]),
+                   h_bf=np_copy(ev.infer.h_bf["on"].view(torch.int16)).view(np.uint16), ret=np_copy(ev.ret),
+                   ep_len=np_copy(ev.ep_len), n_done=np_copy(ev.n_done), len=np_copy(ev.len),
+                   total_done=np_copy(ev.total_done), counted_steps=np_copy(ev.counted_steps), t=np_copy(ev.t_d))
         assert er.check(got, er.EvalRef(lg, K).at(step + 1)) == len(er.EXACT)
     res = ev.result()
     assert res["complete"] and res["episodes"] == K * n and (res["lengths"] == 3).all()
     _report_line("evaluator E 5, 6 steps", worst)
 
 
-def _pong_small(**over):
-    kw = {"replay.burn_in": 4, "replay.learn": 6, "replay.overlap": 5, "replay.n_step": 3,
-          "learner.batch_size": 8, "actor.envs_per_actor": 16, "env.episode_len": 12,
-          "eval.envs": 4, "eval.episodes_per_env": 2}
-    kw.update(over)
-    return get_config("pong", **kw)
-
-
 def test_run_eval_with_fp32_inference(tmp_path):
     from pytorch_r2d2_amd.runner import run_eval
     from pytorch_r2d2_amd.utils.checkpoint import save_reference_checkpoint
-    cfg = _pong_small(**{"eval.compute_dtype": "fp32"})
+    cfg = pong_small(**{"eval.compute_dtype": "fp32"})
     torch.manual_seed(3)
     net = QNet("cpu", cfg.model, cfg.env)
     ckpt = save_reference_checkpoint(net.state_dict(), 7, str(tmp_path / "save"))
@@ -377,57 +302,22 @@ def test_run_eval_with_fp32_inference(tmp_path):
     assert np.array_equal(run_eval(cfg, ckpt, use_graph=False)["returns"], res["returns"])
 
 
-def _engine_state(rp, eng):
-    out = {"master": eng.master, "target": eng.target, "opt_a": eng.opt_a, "opt_b": eng.opt_b,
-           "lstm_b": eng.lstm_b, "lstm_b_t": eng.lstm_b_t, "priority": rp.priority,
-           "tree": rp.tree, "step": rp.step, "loss": eng.loss, "is_start": rp.is_start,
-           "n_valid": rp.n_valid}
-    for tag, (bf, f32) in {"": (eng.bf, eng.f32), "_t": (eng.bf_t, eng.f32_t)}.items():
-        for plane in range(bf.shape[0]):
-            for k, v in eng.layout.packed_views(bf[plane], f32).items():
-                out["%s%s.%d" % (k, tag, plane)] = v
-    return out
-
-
-def _train(evaluate):
-    from pytorch_r2d2_amd.engine.learner_engine import LearnerEngine
-    cfg = get_config("atari57", **{"learner.batch_size": 4, "replay.capacity": 8192, "replay.n_subrings": 4,
-                                   "replay.burn_in": 4, "replay.learn": 4, "replay.overlap": 4,
-                                   "learner.use_graph": False, "env.episode_len": 8,
-                                   "eval.compute_dtype": "fp32"})
-    torch.manual_seed(0)
-    rp = HBMReplay(cfg, torch.device(DEV, 0))
-    rp.fill_synthetic(episode_len=64, seed=0)
-    eng = LearnerEngine(cfg, rp, torch.device(DEV, 0))
-    means = []
-    ev = None
-    if evaluate:
-        ev = BatchedEvaluator(cfg, make_eval_env(cfg, DEV, 4), engine_weights(eng)[0], episodes_per_env=1)
-        assert ev.infer.sp
-    for _ in range(6):
-        eng.step()
-        if ev is not None:
-            res = ev.run()
-            assert res["complete"] and res["episodes"] == 4
-            means.append(res["mean_return"])
-    torch.cuda.synchronize()
-    assert eng.error_word() == 0
-    return rp, eng, means
-
-
 def test_training_is_untouched_by_fp32_evaluations(tmp_path):
     """6 learner steps, once with an fp32 evaluation of the live hi / lo weights after every step:
     master weights, optimizer moments, packed planes, priorities and the tree are bit-equal.  Then
     the driver: run_native(eval_every=2) with an fp32 evaluator logs complete evaluations."""
-    a, b = _train(False), _train(True)
-    sa, sb = _engine_state(a[0], a[1]), _engine_state(b[0], b[1])
+    fp32 = {"eval.compute_dtype": "fp32"}
+    a, b = train_with_evals(False, **fp32), train_with_evals(True, **fp32)
+    sa, sb = engine_state(a[0], a[1]), engine_state(b[0], b[1])
+    sa.update(is_start=a[0].is_start, n_valid=a[0].n_valid)
+    sb.update(is_start=b[0].is_start, n_valid=b[0].n_valid)
     bad = [k for k in sa if not torch.equal(sa[k], sb[k])]
     assert not bad, bad
     assert a[0].total_written == b[0].total_written
     assert a[1].hoist and a[1].hoisted_steps == b[1].hoisted_steps > 0
     assert len(b[2]) == 6 and np.isfinite(b[2]).all()
     from pytorch_r2d2_amd.runner import run_native
-    cfg = _pong_small(**{"eval.compute_dtype": "fp32"})
+    cfg = pong_small(**{"eval.compute_dtype": "fp32"})
     path = str(tmp_path / "m.jsonl")
     out = run_native(cfg, steps=4, eval_every=2, warmup_rows=16 * 40, capacity=16 * 128, log_every=2,
                      metrics_path=path)
@@ -443,7 +333,7 @@ def test_run_native_with_an_fp32_actor(concurrent):
     word (LearnerEngine.check_errors, ConcurrentDriver.check_errors) at its end; the concurrent
     driver's words are also read here."""
     from pytorch_r2d2_amd.runner import run_native
-    cfg = _pong_small(**{"actor.compute_dtype": "fp32"})
+    cfg = pong_small(**{"actor.compute_dtype": "fp32"})
     out = run_native(cfg, steps=6, actor_steps_per_update=2, warmup_rows=16 * 40, capacity=16 * 128,
                      log_every=3, concurrent=concurrent, actor_cus_per_xcd=4 if concurrent else 0,
                      check_every=3)

@@ -6,14 +6,15 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import DEV, NAN, Guarded, dev, dev_bf16
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
 from pytorch_r2d2_amd import lstm_ref as R
+from pytorch_r2d2_amd import refnum as rn
 from pytorch_r2d2_amd.ops._lib import bptt_opts, kernels, ptr, stream_handle
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 PAD = 256                      # guard elements at each end of an output buffer (a multiple of 8)
 EPOCH_FWD, EPOCH_BWD = 3072 + 32, 3072 + 64     # lstm_common.h PT_EPOCH_*
-NAN = float("nan")
 
 
 def _fig(line):
@@ -22,35 +23,8 @@ def _fig(line):
 
 # ---- buffers ---------------------------------------------------------------------------------
 
-class Guarded:
-    """An output buffer between two guard bands, all NaN poison before the launch."""
-
-    def __init__(self, shape, dtype=torch.float32, pad=PAD):
-        self.shape, self.pad = tuple(shape), (pad + 7) // 8 * 8
-        self.n = int(np.prod(self.shape))
-        self.full = torch.full((self.n + 2 * self.pad,), NAN, dtype=dtype, device=DEV)
-        self.body = self.full[self.pad:self.pad + self.n]
-
-    def ptr(self):     # (an empty body still has an address: data_ptr() of an empty view is null)
-        return self.full.data_ptr() + self.pad * self.full.element_size()
-
-    def host_full(self):
-        return self.full.float().cpu().numpy()
-
-    def host(self):
-        return self.body.float().cpu().numpy().reshape(self.shape)
-
-    def bits(self):
-        return self.body.view(torch.int16).cpu().numpy().view(np.uint16).reshape(self.shape)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _dev_bf16(a):
-    """fp32 values that are exact in bf16 -> a bf16 tensor with those bits."""
-    return _dev(R.bf16_bits(a).view(np.int16)).view(torch.bfloat16)
+def _guarded(shape, dtype=torch.float32, pad=PAD):
+    return Guarded(shape, dtype, pad)
 
 
 class Site:
@@ -106,19 +80,19 @@ class FwdRun:
         self.keep, self.outs, words = [], [], []
         for ch in chains:
             ops = R.forward_operands(ch, self.sp)
-            w_hi = _dev_bf16(ops["w_hi"])
-            x, c0 = _dev(ch["xproj"]), _dev(ch["c0"])
-            h0 = _dev(ops["h0"]) if self.sp else _dev_bf16(ops["h0"])
+            w_hi = dev_bf16(ops["w_hi"])
+            x, c0 = dev(ch["xproj"]), dev(ch["c0"])
+            h0 = dev(ops["h0"]) if self.sp else dev_bf16(ops["h0"])
             sf = int(ch["save_from"])
-            o = dict(h_seq=Guarded((T, B, H), torch.bfloat16), c_seq=Guarded((T, B, H)),
-                     h32=Guarded((T, B, H)) if ch["h32"] else None,
-                     gates=Guarded((max(T - sf, 0), B, G), pad=max(PAD, B * G)) if ch["gates"] else None)
+            o = dict(h_seq=_guarded((T, B, H), torch.bfloat16), c_seq=_guarded((T, B, H)),
+                     h32=_guarded((T, B, H)) if ch["h32"] else None,
+                     gates=_guarded((max(T - sf, 0), B, G), pad=max(PAD, B * G)) if ch["gates"] else None)
             w = [ptr(x), ptr(w_hi), ptr(h0), ptr(c0), o["h_seq"].ptr(), o["c_seq"].ptr(),
                  o["h32"].ptr() if o["h32"] else 0, o["gates"].ptr() if o["gates"] else 0, sf]
             self.keep += [w_hi, x, c0, h0]
             if self.sp:
-                w_lo = _dev_bf16(ops["w_lo"])
-                o["h_seq_lo"] = Guarded((T, B, H), torch.bfloat16)
+                w_lo = dev_bf16(ops["w_lo"])
+                o["h_seq_lo"] = _guarded((T, B, H), torch.bfloat16)
                 w += [0 if drop_lo else ptr(w_lo), o["h_seq_lo"].ptr()]
                 self.keep.append(w_lo)
             self.outs.append(o)
@@ -143,7 +117,7 @@ class FwdRun:
             if chains is None or c in chains:
                 for name, g in o.items():
                     if g is not None:
-                        R.check_untouched(f"{label}/chain{c}", name, g.host_full())
+                        g.untouched(f"{label}/chain{c}", name)
 
     def check(self, label, chains):
         """Ownership, then every oracle check; returns the largest use of each bound."""
@@ -152,16 +126,16 @@ class FwdRun:
             lab = f"{label}/chain{c}"
             for name, g in o.items():
                 if g is not None:
-                    R.check_ownership(lab, name, g.host_full(), g.pad)
+                    g.owned(lab, name)
             bits = o["h_seq"].bits()
-            out = dict(h_seq_bits=bits, h_seq=R.bf16_val(bits), c_seq=o["c_seq"].host())
+            out = dict(h_seq_bits=bits, h_seq=rn.bf16_val(bits), c_seq=o["c_seq"].host())
             if o["h32"]:
                 out["h32"] = o["h32"].host()
             if o["gates"]:
                 out["gates"] = o["gates"].host()
             if self.sp:
                 out["h_seq_lo_bits"] = o["h_seq_lo"].bits()
-                out["h_seq_lo"] = R.bf16_val(out["h_seq_lo_bits"])
+                out["h_seq_lo"] = rn.bf16_val(out["h_seq_lo_bits"])
             uses = R.check_forward(lab, ch, out, self.sp)
             worst = {n: max(worst[n], uses[n]) for n in worst}
         return worst
@@ -321,24 +295,24 @@ class BwdRun:
         H, B, T, t0 = bw["H"], bw["B"], bw["T"], bw["t0"]
         K, G, nwg = T - t0, 4 * H, H // 16
         ops = R.backward_operands(bw, self.sp)
-        self.whhT = _dev_bf16(R.pack_whh_t(ops["w_hi"]))
-        self.whhT_lo = _dev_bf16(R.pack_whh_t(ops["w_lo"])) if self.sp else None
-        self.gates, self.cseq, self.c0 = _dev(bw["gates"]), _dev(bw["c_seq"]), _dev(bw["c0"])
+        self.whhT = dev_bf16(R.pack_whh_t(ops["w_hi"]))
+        self.whhT_lo = dev_bf16(R.pack_whh_t(ops["w_lo"])) if self.sp else None
+        self.gates, self.cseq, self.c0 = dev(bw["gates"]), dev(bw["c_seq"]), dev(bw["c0"])
         self.dz = None
         if bw.get("dz_hi") is not None:
             # dh_ext is not read on the dz path: a NaN buffer shows it
             self.dh = torch.full((K, B, H), NAN, device=DEV)
-            self.dz = [_dev_bf16(bw[n]) for n in ("dz_hi", "dz_lo", "w1t_hi", "w1t_lo")]
+            self.dz = [dev_bf16(bw[n]) for n in ("dz_hi", "dz_lo", "w1t_hi", "w1t_lo")]
         else:
-            self.dh = _dev(bw["dh_ext"]) if bw["dh_ext"] is not None else None
+            self.dh = dev(bw["dh_ext"]) if bw["dh_ext"] is not None else None
         row = max(PAD, B * G)      # one more step's rows of guard: dgates beyond T - t0 steps
-        self.out = dict(dgates=Guarded((K, B, G), torch.bfloat16, pad=row))
+        self.out = dict(dgates=_guarded((K, B, G), torch.bfloat16, pad=row))
         if self.sp and not drop_dgates_lo:
-            self.out["dgates_lo"] = Guarded((K, B, G), torch.bfloat16, pad=row)
+            self.out["dgates_lo"] = _guarded((K, B, G), torch.bfloat16, pad=row)
         if entry.startswith("tag"):
-            self.out["db1"], self.out["db2"] = Guarded((G,)), Guarded((G,))
+            self.out["db1"], self.out["db2"] = _guarded((G,)), _guarded((G,))
             self.bias_ws = torch.zeros((B + 15) // 16, G, device=DEV)
-            self.perm = _dev(R.gate_perm(H).astype(np.int32))
+            self.perm = dev(R.gate_perm(H).astype(np.int32))
         elif entry == "step":
             self.s0 = torch.zeros(nwg, B, H, device=DEV)
             self.s1 = torch.zeros(nwg, B, H, device=DEV)
@@ -379,17 +353,17 @@ class BwdRun:
 
     def assert_untouched(self, label):
         for name, g in self.out.items():
-            R.check_untouched(label, name, g.host_full())
+            g.untouched(label, name)
 
     def check(self, label):
         o = self.out
         for name, g in o.items():
-            R.check_ownership(label, name, g.host_full(), g.pad)
+            g.owned(label, name)
         bits = o["dgates"].bits()
-        out = dict(dgates_bits=bits, dgates=R.bf16_val(bits))
+        out = dict(dgates_bits=bits, dgates=rn.bf16_val(bits))
         if self.sp:
             out["dgates_lo_bits"] = o["dgates_lo"].bits()
-            out["dgates_lo"] = R.bf16_val(out["dgates_lo_bits"])
+            out["dgates_lo"] = rn.bf16_val(out["dgates_lo_bits"])
         use, ref = R.check_backward(label, self.bw, out, self.sp)
         ub = 0.0
         if "db1" in o:
@@ -487,13 +461,13 @@ def test_backward_head_gradient_job(entry, A):
     site = _bwd_site(entry, 16, 256)
     assert plain.launch(site) == 0
     site.check(label + "/plain", True, EPOCH_BWD)
-    dva = _dev(hc["dva"])
+    dva = dev(hc["dva"])
     if sp:
-        hi, lo = R.split_planes(hc["dz"])
-        ins = [dva, _dev(hc["zr"]), _dev_bf16(hi), _dev_bf16(lo)]
+        hi, lo = rn.split_planes(hc["dz"])
+        ins = [dva, dev(hc["zr"]), dev_bf16(hi), dev_bf16(lo)]
     else:
-        ins = [dva, _dev_bf16(R.bf16_round(hc["zr"])), _dev_bf16(R.bf16_round(hc["dz"]))]
-    outs = dict(gw2=Guarded((1 + A, 64)), gb2=Guarded((1 + A,)), gb1=Guarded((128,)))
+        ins = [dva, dev_bf16(rn.bf16_round(hc["zr"])), dev_bf16(rn.bf16_round(hc["dz"]))]
+    outs = dict(gw2=_guarded((1 + A, 64)), gb2=_guarded((1 + A,)), gb1=_guarded((128,)))
     ws = torch.zeros(int(k.r2_gradsum_ws_floats()), device=DEV)
     ticket = torch.zeros(64, dtype=torch.int32, device=DEV)
     hg = [ptr(t) for t in ins] + [g.ptr() for g in outs.values()] + [hc["N"], A, 64, ptr(ws), ptr(ticket)]
@@ -506,7 +480,7 @@ def test_backward_head_gradient_job(entry, A):
     for a, b in zip(plain.device_outputs(), run.device_outputs()):
         assert torch.equal(a.view(torch.int16), b.view(torch.int16)), f"{label}: the side job changed dgates / db"
     for name, g in outs.items():
-        R.check_ownership(label, name, g.host_full(), g.pad)
+        g.owned(label, name)
     uh = R.check_head_grads(label, hc, {n: g.host() for n, g in outs.items()}, sp)
     _fig(f"{label:22s} dgates {use:.3f}  db {ub:.3f}  head {uh:.3f}")
 
@@ -522,8 +496,8 @@ def test_backward_refusals(what):
     if what == "dz at H 128":      # b_burn's shape with dz operands of the matching width
         rng = np.random.default_rng(3)
         K = bw["T"] - bw["t0"]
-        bw["dz_hi"], bw["dz_lo"] = R.split_planes((0.2 * rng.standard_normal((K * bw["B"], R.DZ_K))).astype(np.float32))
-        bw["w1t_hi"], bw["w1t_lo"] = R.split_planes((0.2 * rng.standard_normal((bw["H"], R.DZ_K))).astype(np.float32))
+        bw["dz_hi"], bw["dz_lo"] = rn.split_planes((0.2 * rng.standard_normal((K * bw["B"], R.DZ_K))).astype(np.float32))
+        bw["w1t_hi"], bw["w1t_lo"] = rn.split_planes((0.2 * rng.standard_normal((bw["H"], R.DZ_K))).astype(np.float32))
     entry = "tag" if what in ("dz through the bf16 entry", "bias_ws without perm") else "tag_sp"
     run = BwdRun(entry, bw, drop_dgates_lo=what == "sp without dgates_lo")
     site = _bwd_site(entry, bw["B"], bw["H"])
@@ -543,7 +517,7 @@ def test_backward_refusals(what):
     else:
         _, bw = R.backward_case("b_hg")
         run, site = BwdRun("tag", bw), _bwd_site("tag", 16, 256)
-        extra = {n: Guarded((4096,)) for n in ("dva", "zr", "dz", "gw2", "gb2", "gb1", "ws", "ticket")}
+        extra = {n: _guarded((4096,)) for n in ("dva", "zr", "dz", "gw2", "gb2", "gb1", "ws", "ticket")}
         hg = [extra[n].ptr() for n in ("dva", "zr", "dz", "gw2", "gb2", "gb1")] + [40, 9, 96,
                                                                                   extra["ws"].ptr(), extra["ticket"].ptr()]
         rc, code = run.launch(site, hg=hg), -5
@@ -551,5 +525,5 @@ def test_backward_refusals(what):
     torch.cuda.synchronize()
     run.assert_untouched(what)
     for name, g in extra.items():
-        R.check_untouched(what, name, g.host_full())
+        g.untouched(what, name)
     assert not site.ctr.any() and int(site.err.item()) == 0

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from pytorch_r2d2_amd import lstm_ref as R
+from pytorch_r2d2_amd import refnum as rn
 
 FWD = list(R.FORWARD_CASES)
 BWD = list(R.BACKWARD_CASES)
@@ -73,9 +74,9 @@ def test_untied_oracle_is_float64_lstmcell_and_autograd():
 
 def test_number_formats_match_torch():
     x = torch.randn(4096) * torch.logspace(-6, 4, 4096)
-    bits = R.bf16_bits(x.numpy())
+    bits = rn.bf16_bits(x.numpy())
     assert np.array_equal(bits.view(np.int16), x.bfloat16().view(torch.int16).numpy())
-    hi, lo = R.split_planes(x.numpy())
+    hi, lo = rn.split_planes(x.numpy())
     assert np.array_equal(lo, (x - x.bfloat16().float()).bfloat16().float().numpy())
     assert (np.abs(hi.astype(np.float64) + lo - x.numpy()) <= 2.0 ** -17 * x.abs().numpy()).all()
     r = R.round19(x.numpy())
@@ -216,7 +217,7 @@ def test_forward_mutation_is_rejected(mut):
                         out[k][:, -1] = out[k][:, -2]
             elif mut == "h32_bf16":
                 for out in outs:
-                    out["h32"] = R.bf16_round(out["h32"])
+                    out["h32"] = rn.bf16_round(out["h32"])
             elif mut == "h_seq_lo_zero":
                 for out in outs:
                     out["h_seq_lo"][:] = 0
@@ -286,18 +287,18 @@ def test_ownership_check_has_teeth():
     buf = np.full(pad + n + pad, np.nan, np.float32)
     valid = np.arange(n) < 16
     buf[pad:pad + 16] = 1.0
-    R.check_ownership("own", "gates", buf, pad, valid)
+    rn.check_ownership("own", "gates", buf, pad, valid)
     for i, what in ((pad - 1, "guard before"), (pad + n, "guard after"), (pad + 20, "does not own")):
         b = buf.copy()
         b[i] = 0.0
         with pytest.raises(AssertionError, match=what):
-            R.check_ownership("own", "gates", b, pad, valid)
+            rn.check_ownership("own", "gates", b, pad, valid)
     b = buf.copy()
     b[pad + 3] = np.nan
     with pytest.raises(AssertionError, match="not written"):
-        R.check_ownership("own", "gates", b, pad, valid)
+        rn.check_ownership("own", "gates", b, pad, valid)
     with pytest.raises(AssertionError):
-        R.check_untouched("own", "gates", buf)
+        rn.check_untouched("own", "gates", buf)
 
 
 @pytest.mark.parametrize("A", [1, 9])

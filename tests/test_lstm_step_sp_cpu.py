@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from pytorch_r2d2_amd import lstm_ref as R
+from pytorch_r2d2_amd import refnum as rn
 
 
 def _emulate(ch, T, drop_lo=False):
@@ -21,7 +22,7 @@ def _emulate(ch, T, drop_lo=False):
     cs, hs, gs = [], [], []
     h = ops["h0"]
     for t in range(T):
-        a_hi, a_lo = R.split_planes(h)
+        a_hi, a_lo = rn.split_planes(h)
         if drop_lo:
             pre = R._mm32(a_hi, None, ops["w_hi"], None, 64)
         else:
@@ -35,10 +36,10 @@ def _emulate(ch, T, drop_lo=False):
         g[:, col[0]], g[:, col[1]], g[:, col[2]], g[:, col[3]] = gi, gf, gg, go
         cs.append(c), hs.append(h), gs.append(g)
     h32 = np.stack(hs)
-    hi = R.bf16_round(h32)
+    hi = rn.bf16_round(h32)
     lo = (h32 - hi).astype(np.float32)
-    return dict(c_seq=np.stack(cs), h32=h32, h_seq_bits=R.bf16_bits(h32), h_seq=hi,
-                h_seq_lo_bits=R.bf16_bits(lo), h_seq_lo=R.bf16_round(lo),
+    return dict(c_seq=np.stack(cs), h32=h32, h_seq_bits=rn.bf16_bits(h32), h_seq=hi,
+                h_seq_lo_bits=rn.bf16_bits(lo), h_seq_lo=rn.bf16_round(lo),
                 gates=np.stack(gs)[sf:] if sf < T else np.zeros((0, B, 4 * H), np.float32))
 
 
@@ -60,7 +61,7 @@ def test_bf16_shortcuts_are_rejected(name):
     ch = chains[0]
     with pytest.raises(AssertionError):          # hi.hi only
         R.check_forward(f"{name}/drop_lo", ch, _emulate(ch, spec["T"], drop_lo=True), sp=True)
-    rounded = dict(ch, h0=R.bf16_round(ch["h0"]))
+    rounded = dict(ch, h0=rn.bf16_round(ch["h0"]))
     with pytest.raises(AssertionError):          # h0 through bf16, as the bf16 path carries it
         R.check_forward(f"{name}/h0_bf16", ch, R.emulate_forward(rounded, True, spec["T"]), sp=True)
 

@@ -8,58 +8,22 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import Guarded, dev, dev_bf16
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
 from pytorch_r2d2_amd import lstm_ref as R
+from pytorch_r2d2_amd import refnum as rn
 from pytorch_r2d2_amd.ops._lib import kernels, ptr, stream_handle
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 PAD = 256
-NAN = float("nan")
 
 
 def _fig(line):
     print("lstm-step-sp: " + line)
 
 
-@pytest.fixture(autouse=True)
-def _stop_after_a_gpu_error():
-    """A launch that faulted leaves the device in an error state: nothing more is launched."""
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"GPU error, no further launches: {e}", returncode=3)
-
-
-class Guarded:
-    """An output buffer between two guard bands, all NaN poison before the launch."""
-
-    def __init__(self, shape, dtype=torch.float32, pad=PAD):
-        self.shape, self.pad = tuple(shape), (pad + 7) // 8 * 8
-        self.n = int(np.prod(self.shape))
-        self.esz = 2 if dtype == torch.bfloat16 else 4
-        self.full = torch.full((self.n + 2 * self.pad,), NAN, dtype=dtype, device=DEV)
-        self.body = self.full[self.pad:self.pad + self.n]
-
-    def ptr(self, elem=0):
-        return self.full.data_ptr() + (self.pad + elem) * self.esz
-
-    def host_full(self):
-        return self.full.float().cpu().numpy()
-
-    def host(self):
-        return self.body.float().cpu().numpy().reshape(self.shape)
-
-    def bits(self):
-        return self.body.view(torch.int16).cpu().numpy().view(np.uint16).reshape(self.shape)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _dev_bf16(a):
-    return _dev(R.bf16_bits(a).view(np.int16)).view(torch.bfloat16)
+def _guarded(shape, dtype=torch.float32, pad=PAD):
+    return Guarded(shape, dtype, pad)
 
 
 class StepRun:
@@ -82,17 +46,17 @@ class StepRun:
             x = np.concatenate([ch["xproj"] for ch in mine] +
                                [np.zeros((T, NR - B * len(mine), G), np.float32)], axis=1)
             self.nets[n] = dict(
-                w_hi=_dev_bf16(ops["w_hi"]), w_lo=_dev_bf16(ops["w_lo"]), x=_dev(x),
-                h0=_dev(np.concatenate([ch["h0"] for ch in mine] + pad_rows[:1])),
-                c0=_dev(np.concatenate([ch["c0"] for ch in mine] + pad_rows[1:])),
-                h_seq=Guarded((T, NR, H), torch.bfloat16), h_seq_lo=Guarded((T, NR, H), torch.bfloat16),
-                c_seq=Guarded((T, NR, H)), h32=Guarded((T, NR, H)) if mine[0]["h32"] else None, NR=NR)
+                w_hi=dev_bf16(ops["w_hi"]), w_lo=dev_bf16(ops["w_lo"]), x=dev(x),
+                h0=dev(np.concatenate([ch["h0"] for ch in mine] + pad_rows[:1])),
+                c0=dev(np.concatenate([ch["c0"] for ch in mine] + pad_rows[1:])),
+                h_seq=_guarded((T, NR, H), torch.bfloat16), h_seq_lo=_guarded((T, NR, H), torch.bfloat16),
+                c_seq=_guarded((T, NR, H)), h32=_guarded((T, NR, H)) if mine[0]["h32"] else None, NR=NR)
             self.inputs += [(f"net{n}/{k}", self.nets[n][k], self.nets[n][k].clone())
                             for k in ("h0", "c0", "x", "w_hi", "w_lo")]
         for i, ch in enumerate(chains):
             N = self.nets[ch.get("net", i)]
             r0, sf = ch.get("row0", 0), int(ch["save_from"])
-            g = Guarded((max(T - sf, 0), B, G), pad=max(PAD, B * G)) if ch["gates"] else None
+            g = _guarded((max(T - sf, 0), B, G), pad=max(PAD, B * G)) if ch["gates"] else None
             self.gates.append(g)
             w = [ptr(N["x"]) + r0 * G * 4, ptr(N["w_hi"]), ptr(N["h0"]) + r0 * H * 4,
                  ptr(N["c0"]) + r0 * H * 4, N["h_seq"].ptr(r0 * H), N["c_seq"].ptr(r0 * H),
@@ -118,7 +82,7 @@ class StepRun:
     def assert_untouched(self, label, only=None):
         for name, g in self.buffers():
             if only is None or name.startswith(only):
-                R.check_untouched(label, name, g.host_full())
+                g.untouched(label, name)
 
     def assert_inputs_untouched(self, label):
         for name, t, before in self.inputs:
@@ -139,21 +103,21 @@ class StepRun:
                 valid[:] = True
             for name in ("h_seq", "h_seq_lo", "c_seq", "h32"):
                 if N[name] is not None:
-                    R.check_ownership(f"{label}/net{n}", name, N[name].host_full(), N[name].pad, valid)
+                    N[name].owned(f"{label}/net{n}", name, valid)
         for i, (ch, g) in enumerate(zip(self.chains, self.gates)):
             lab = f"{label}/chain{i}"
             N = self.nets[ch.get("net", i)]
             r0 = ch.get("row0", 0)
             if g is not None:
-                R.check_ownership(lab, "gates", g.host_full(), g.pad)
+                g.owned(lab, "gates")
 
             def cut(a, NR=N["NR"], r0=r0):
                 if self.loose:      # launched on the first B rows of a larger (T = 1) buffer
                     return np.ascontiguousarray(a.reshape(-1)[: B * self.H].reshape(1, B, self.H))
                 return np.ascontiguousarray(a.reshape(self.T, NR, self.H)[:, r0:r0 + B])
             bits, lo_bits = cut(N["h_seq"].bits()), cut(N["h_seq_lo"].bits())
-            out = dict(h_seq_bits=bits, h_seq=R.bf16_val(bits), h_seq_lo_bits=lo_bits,
-                       h_seq_lo=R.bf16_val(lo_bits), c_seq=cut(N["c_seq"].host()))
+            out = dict(h_seq_bits=bits, h_seq=rn.bf16_val(bits), h_seq_lo_bits=lo_bits,
+                       h_seq_lo=rn.bf16_val(lo_bits), c_seq=cut(N["c_seq"].host()))
             if N["h32"] is not None:
                 out["h32"] = cut(N["h32"].host())
             if g is not None:

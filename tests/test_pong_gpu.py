@@ -13,10 +13,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import DEV, NAN, Buf, packed_weights
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
 from pytorch_r2d2_amd import pong_ref as pr
-from pytorch_r2d2_amd.actor_batched import BatchedActor, PackedWeights
+from pytorch_r2d2_amd.actor_batched import BatchedActor
 from pytorch_r2d2_amd.config import get_config
-from pytorch_r2d2_amd.engine.layout import ParamLayout
 from pytorch_r2d2_amd.engine.replay_hbm import HBMReplay
 from pytorch_r2d2_amd.envs import VecPong, make_device_env
 from pytorch_r2d2_amd.envs.pong_device import PongArgs
@@ -25,22 +26,10 @@ from pytorch_r2d2_amd.models import QNet
 from pytorch_r2d2_amd.ops._lib import kernels, stream_handle
 from pytorch_r2d2_amd.utils.metrics import read_jsonl
 from test_pong_ref_cpu import RUN, SEED, STEPS, compare_run, scripted_case
-from test_replay_oracle_gpu import DEV, Buf
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 PLANE = 84 * 84
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_gpu_error():
-    """A launch that faulted leaves the device in an error state: nothing more is launched."""
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"GPU error, no further launches: {e}", returncode=3)
 
 
 class Launch:
@@ -135,16 +124,9 @@ def _cfg(preset="reference", **over):
     return get_config(preset, **kw)
 
 
-def _weights(cfg, seed):
-    torch.manual_seed(seed)
-    w = PackedWeights(ParamLayout(cfg.model, cfg.env), DEV)
-    w.load(QNet("cpu", cfg.model, cfg.env).state_dict())
-    return w
-
-
 def _actor_run(cfg, graph, steps=40, E=4):
     rp = HBMReplay(cfg, torch.device(DEV, 0), capacity=E * 128, n_subrings=E)
-    w = _weights(cfg, 0)
+    w = packed_weights(cfg, 0)[1]
     env = make_device_env(cfg, E, DEV, seed=3, randomize_start=False)
     assert type(env) is VecPong and env.fused
     actor = BatchedActor(cfg, rp, env, w, w, seed=1)
@@ -178,7 +160,7 @@ def test_actor_on_pong_eager_and_captured_agree():
 def test_evaluator_on_pong_counts_the_env_s_rewards():
     n, k = 4, 2
     cfg = _cfg("atari57")
-    w = _weights(cfg, 5)
+    w = packed_weights(cfg, 5)[1]
     ev = BatchedEvaluator(cfg, make_eval_env(cfg, DEV, n, seed=11), w, episodes_per_env=k, seed=11,
                           epsilon=[0.0, 0.3, 0.6, 1.0])
     assert type(ev.env) is VecPong and ev.can_capture and not ev.env.randomize_start

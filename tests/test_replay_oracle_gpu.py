@@ -9,12 +9,12 @@ CPU that the checks reject wrong kernels.
 
 With R2D2_REPLAY_ORACLE_REPORT=<file> the measured figures are written there
 (profiles/replay_oracle_errors.txt)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from gpu_support import DEV, G, NAN, Buf, Tree, i64, report_fixture, word
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
 from pytorch_r2d2_amd import replay_ref as rr
 from pytorch_r2d2_amd.ops._lib import kernels, stream_handle
 from test_replay_ref_cpu import (CTRS, EDIT_T, ETA, GEOMS, SAMPLER_CASES, SEEDS, TUPD, FLAG_KINDS,
@@ -23,118 +23,14 @@ from test_replay_ref_cpu import (CTRS, EDIT_T, ETA, GEOMS, SAMPLER_CASES, SEEDS,
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-G = 16
-NAN = float("nan")
-_REPORT = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    path = os.environ.get("R2D2_REPLAY_ORACLE_REPORT")
-    if path and _REPORT:
-        with open(path, "w") as f:
-            f.write("# replay.hip against replay_ref.py, one line per case\n"
-                    "# sample : largest miss (distance from the float64 draw point to the returned\n"
-                    "#          leaf's mass interval / total; the bound is d), share of draws for which\n"
-                    "#          d admits a second leaf, draws that differ from the float64 sampler\n"
-                    "# refresh / mark / pending : largest relative leaf error in units of 2^-24, and\n"
-                    "#          the bound in the same units\n")
-            for line in _REPORT:
-                f.write(line + "\n")
-
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_gpu_error():
-    """A launch that faulted leaves the device in an error state: nothing more is launched."""
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"GPU error, no further launches: {e}", returncode=3)
-
-
-class Buf:
-    """A device buffer between two runs of G guard elements; ``p`` points at the body."""
-
-    def __init__(self, body, poison):
-        if not torch.is_tensor(body):
-            body = torch.from_numpy(np.ascontiguousarray(body))
-        body = body.reshape(-1)
-        g = torch.full((G,), poison, dtype=body.dtype)
-        self.full = torch.cat([g, body, g]).to(DEV)
-        self.init = self.full.clone()
-        self.n = body.numel()
-
-    @classmethod
-    def poisoned(cls, n, dtype, poison):
-        return cls(torch.full((n,), poison, dtype=dtype), poison)
-
-    @property
-    def p(self):
-        return self.full.data_ptr() + G * self.full.element_size()
-
-    @staticmethod
-    def _bytes(t):
-        return t.detach().cpu().contiguous().view(torch.uint8).reshape(-1).numpy()
-
-    def bits(self):
-        """Bytes of the body."""
-        return self._bytes(self.full[G: G + self.n])
-
-    def body(self):
-        return self.full[G: G + self.n].cpu().numpy()
-
-    def tail(self, init=False):
-        """Body and back guard (leaf i at index i)."""
-        return (self.init if init else self.full)[G:].cpu().numpy()
-
-    def assert_guards(self, what=""):
-        a, b = self._bytes(self.full), self._bytes(self.init)
-        e = G * self.full.element_size()
-        assert np.array_equal(a[:e], b[:e]), f"{what}: front guard overwritten"
-        assert np.array_equal(a[-e:], b[-e:]), f"{what}: back guard overwritten"
-
-    def assert_untouched(self, what=""):
-        assert np.array_equal(self._bytes(self.full), self._bytes(self.init)), f"{what}: written"
-
-
-def _i64(x):
-    return np.ascontiguousarray(np.asarray(x, dtype=np.int64))
-
-
-def _word(v, dtype=torch.int32):
-    return torch.tensor([v], dtype=dtype, device=DEV)
-
-
-class Tree:
-    """A guarded device tree over ``leaves``, rebuilt by r2_tree_rebuild and checked."""
-
-    def __init__(self, leaves):
-        self.leaves = np.asarray(leaves, dtype=np.float32)
-        offs, sizes = rr.tree_geometry(self.leaves.size)
-        self.offs, self.sizes, self.levels = _i64(offs), _i64(sizes), len(sizes)
-        body = np.full(offs[-1] + sizes[-1], np.nan, dtype=np.float32)
-        body[: self.leaves.size] = self.leaves
-        self.buf = Buf(body, NAN)
-        assert kernels().r2_tree_rebuild(*self.geom(), stream_handle()) == 0
-        torch.cuda.synchronize()
-        self.check()
-        self.buf.init = self.buf.full.clone()
-
-    def geom(self):
-        return self.buf.p, self.offs.ctypes.data, self.sizes.ctypes.data, self.levels
-
-    def host(self):
-        return self.buf.body()
-
-    def root(self):
-        return float(self.host()[self.offs[-1]])
-
-    def check(self, leaves=None):
-        self.buf.assert_guards("tree")
-        return rr.check_tree(self.host(), self.offs.tolist(), self.sizes.tolist(), leaves)
+_REPORT, _report = report_fixture(
+    "R2D2_REPLAY_ORACLE_REPORT",
+    "# replay.hip against replay_ref.py, one line per case\n"
+    "# sample : largest miss (distance from the float64 draw point to the returned\n"
+    "#          leaf's mass interval / total; the bound is d), share of draws for which\n"
+    "#          d admits a second leaf, draws that differ from the float64 sampler\n"
+    "# refresh / mark / pending : largest relative leaf error in units of 2^-24, and\n"
+    "#          the bound in the same units\n")
 
 
 _TREES = {}
@@ -157,7 +53,7 @@ def test_tree_sample_draws_against_the_cdf(name):
     for B in c["Bs"]:
         for seed in SEEDS:
             for ctr in CTRS:
-                step = _word(ctr, torch.int64)
+                step = word(ctr, torch.int64)
                 idx, prob = Buf.poisoned(B, torch.int32, -1), Buf.poisoned(B, torch.float32, NAN)
                 assert k.r2_tree_sample(*tree.geom(), B, seed, step.data_ptr(), idx.p, prob.p,
                                         stream_handle()) == 0
@@ -204,7 +100,7 @@ def test_tree_without_mass_gives_rows_in_range_and_probability_zero(cap):
     assert tree.root() == 0.0
     B = 64
     idx, prob = Buf.poisoned(B, torch.int32, -1), Buf.poisoned(B, torch.float32, NAN)
-    step = _word(3, torch.int64)
+    step = word(3, torch.int64)
     assert kernels().r2_tree_sample(*tree.geom(), B, SEEDS[0], step.data_ptr(), idx.p, prob.p,
                                     stream_handle()) == 0
     torch.cuda.synchronize()
@@ -220,7 +116,7 @@ def _state_setup(cap, H, nstate, h_f32, B, seed=5):
     dsrc = [s.to(DEV) for s in src]
     h = [Buf.poisoned(B * H, torch.float32 if h_f32 else torch.bfloat16, NAN) for _ in range(nstate)]
     c = [Buf.poisoned(B * H, torch.float32, NAN) for _ in range(nstate)]
-    arr = lambda xs: _i64(list(xs) + [0])     # noqa: E731
+    arr = lambda xs: i64(list(xs) + [0])     # noqa: E731
     ptrs = dict(hs=arr(s.data_ptr() for s in dsrc), h=arr(b.p for b in h), c=arr(b.p for b in c))
     return src, dsrc, h, c, ptrs
 
@@ -277,7 +173,7 @@ def test_sample_batch_draws_rows_and_states(entry, geom, Tn, nstate, H, h_f32, c
     off = np.asarray(offs + [0], dtype=np.int32)
     starts, probs = Buf.poisoned(B, torch.int32, -1), Buf.poisoned(B, torch.float32, NAN)
     rows = Buf.poisoned(Tn * B, torch.int32, -1)
-    step = _word(ctr, torch.int64)
+    step = word(ctr, torch.int64)
     q = Buf(np.full(4, 7, dtype=np.int32), -1)
     args = (*tree.geom(), B, seed, step.data_ptr(), starts.p, probs.p, rows.p, Tn, cap_e, H, nstate,
             ptrs["hs"].ctypes.data, off.ctypes.data, ptrs["h"].ctypes.data, ptrs["c"].ctypes.data)
@@ -305,14 +201,14 @@ def test_sample_batch_draws_rows_and_states(entry, geom, Tn, nstate, H, h_f32, c
 @pytest.mark.parametrize("levels", [1, 9])
 def test_sampler_refuses_a_tree_depth_it_cannot_hold(levels):
     tree = batch_tree(3, 257)
-    offs, sizes = _i64(list(tree.offs) + [0] * 9), _i64(list(tree.sizes) + [1] * 9)
+    offs, sizes = i64(list(tree.offs) + [0] * 9), i64(list(tree.sizes) + [1] * 9)
     geom = (tree.buf.p, offs.ctypes.data, sizes.ctypes.data, levels)
     B, Tn, H = 8, 4, 64
     idx, prob = Buf.poisoned(B, torch.int32, -1), Buf.poisoned(B, torch.float32, NAN)
     rows = Buf.poisoned(Tn * B, torch.int32, -1)
-    step = _word(0, torch.int64)
+    step = word(0, torch.int64)
     assert kernels().r2_tree_sample(*geom, B, 1, step.data_ptr(), idx.p, prob.p, stream_handle()) == -1
-    z = _i64([0])
+    z = i64([0])
     zi = np.zeros(1, dtype=np.int32)
     for entry in ("r2_sample_batch", "r2_sample_batch_f32h"):
         assert getattr(kernels(), entry)(*geom, B, 1, step.data_ptr(), idx.p, prob.p, rows.p, Tn, 257, H,
@@ -366,7 +262,7 @@ class RefreshRun:
         self.priority = Buf(c["priority"], NAN)
         self.starts = torch.from_numpy(c["starts"]).to(DEV)
         self.dirty = Buf.poisoned(max_dirty, torch.int32, -1)
-        self.count = _word(0)
+        self.count = word(0)
         self.max_dirty = max_dirty
 
     def refresh_args(self, leaves_p, T=None, upd=None):
@@ -428,7 +324,7 @@ def test_prio_tail_against_the_oracle(tupd):
         tree = run.tree
         assert tree.levels == 4
         sync = torch.zeros(8, dtype=torch.int32, device=DEV)
-        step = _word(41, torch.int64)
+        step = word(41, torch.int64)
         a = run.refresh_args(0)
         rc = kernels().r2_prio_tail(*a[:4], *tree.geom(), *a[5:], sync.data_ptr(), step.data_ptr(), 1,
                                     stream_handle())
@@ -462,7 +358,7 @@ def test_refresh_with_a_candidate_list_just_inside_its_limit():
     rc = kernels().r2_seqprio_refresh(*run.refresh_args(run.tree.buf.p, T=1025, upd=(0, 1025)),
                                       stream_handle())
     assert rc == -2
-    sync, step = torch.zeros(8, dtype=torch.int32, device=DEV), _word(0, torch.int64)
+    sync, step = torch.zeros(8, dtype=torch.int32, device=DEV), word(0, torch.int64)
     a = run.refresh_args(0, T=1025, upd=(0, 1025))
     assert kernels().r2_prio_tail(*a[:4], *run.tree.geom(), *a[5:], sync.data_ptr(), step.data_ptr(), 1,
                                   stream_handle()) == -2
@@ -509,8 +405,8 @@ def test_prio_tail_sample_draws_from_the_repaired_tree():
     s_rows = Buf.poisoned(Tn * B, torch.int32, -1)
     sync = torch.zeros(8, dtype=torch.int32, device=DEV)
     step0 = 2 ** 33 - 1
-    step = _word(step0, torch.int64)
-    wait = _word(1)
+    step = word(step0, torch.int64)
+    wait = word(1)
     q = Buf(np.full(4, 7, dtype=np.int32), -1)
     a = run.refresh_args(0)
     rc = kernels().r2_prio_tail_sample(*a[:4], *tree.geom(), *a[5:], sync.data_ptr(), step.data_ptr(),
@@ -547,8 +443,8 @@ class EditRun:
         self.leaves = Buf(c["leaves"], NAN)
         self.priority = Buf(c["priority"], NAN)
         self.dirty = Buf.poisoned(256, torch.int32, -1)
-        self.count = _word(0)
-        self.n_valid = _word(100)
+        self.count = word(0)
+        self.n_valid = word(100)
 
     def check(self, ref, T):
         self.flags.assert_guards("flags")
@@ -569,7 +465,7 @@ def test_mark_starts_against_the_oracle(T):
     d_rows = torch.from_numpy(rows).to(DEV)
     for n_rows in (None, len(rows) - 4, len(rows) + 9):
         run = EditRun(c)
-        n_dev = None if n_rows is None else _word(n_rows)
+        n_dev = None if n_rows is None else word(n_rows)
         rc = kernels().r2_mark_starts(d_rows.data_ptr(), 0 if n_dev is None else n_dev.data_ptr(),
                                       len(rows), run.flags.p, run.priority.p, run.leaves.p, T,
                                       c["cap_e"], ETA, run.n_valid.data_ptr(), run.dirty.p,
@@ -591,7 +487,7 @@ def test_apply_pending_against_the_oracle(T):
     d_pend = torch.from_numpy(pend).to(DEV)
     for cnt, cap_p in ((len(pend), len(pend) + 3), (len(pend) + 5, len(pend) - 3)):
         run = EditRun(c)
-        d_cnt, err = _word(cnt), _word(0)
+        d_cnt, err = word(cnt), word(0)
         rc = kernels().r2_apply_pending(d_pend.data_ptr(), d_cnt.data_ptr(), cap_p, run.flags.p,
                                         run.priority.p, run.leaves.p, T, c["cap_e"], ETA,
                                         run.n_valid.data_ptr(), run.dirty.p, run.count.data_ptr(), 256,

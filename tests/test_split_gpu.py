@@ -6,47 +6,32 @@ import copy
 import pytest
 import torch
 
+from gpu_support import rand_operand, rel_err, split_bf16
 from pytorch_r2d2_amd.ops.gemm import Gemm, gemm, gemm_group, group_ws_bytes
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 
 
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-def _split(x):
-    hi = x.to(torch.bfloat16)
-    lo = (x - hi.float()).to(torch.bfloat16)
-    return hi, lo
-
-
-def _op(rows, cols, kmajor, gen):
-    x = torch.randn(rows, cols, generator=gen, device=DEV)
-    return x if kmajor else x.t().contiguous().t()
-
-
 @pytest.mark.parametrize("ak,bk", [(1, 1), (1, 0), (0, 0)])
 @pytest.mark.parametrize("M,N,K", [(5440, 1024, 1568), (2560, 512, 256), (304, 200, 128), (2560, 256, 512)])
 def test_split_gemm_is_fp32_accurate(ak, bk, M, N, K):
     g = torch.Generator(device=DEV).manual_seed(M + N + K + ak)
-    a = _op(M, K, ak, g)
-    b = _op(N, K, bk, g).t()
-    ah, al = _split(a)
-    bh, bl = _split(b)
+    a = rand_operand(M, K, ak, g)
+    b = rand_operand(N, K, bk, g).t()
+    ah, al = split_bf16(a)
+    bh, bl = split_bf16(b)
     c = torch.empty(M, N, device=DEV)
     bias = torch.randn(N, generator=g, device=DEV)
     gemm(Gemm(ah, bh, c, bias=bias, a_lo=al, b_lo=bl))
     ref = a.double() @ b.double() + bias.double()
     torch.cuda.synchronize()
-    r = _rel(c, ref)
+    r = rel_err(c, ref)
     assert r < 2e-5, r
     # bf16 operands alone are ~1e-3 off: the lo passes are what buys the accuracy
     c1 = torch.empty(M, N, device=DEV)
     gemm(Gemm(ah, bh, c1, bias=bias))
-    assert _rel(c1, ref) > 20 * r
+    assert rel_err(c1, ref) > 20 * r
 
 
 def test_split_gemm_split_output_and_group():
@@ -54,21 +39,21 @@ def test_split_gemm_split_output_and_group():
     operands, K split 1 and 2 ways."""
     g = torch.Generator(device=DEV).manual_seed(5)
     M, N, K = 2560, 1568, 1024
-    a, b = _op(M, K, 1, g), _op(N, K, 0, g).t()
-    ah, al = _split(a)
-    bh, bl = _split(b)
+    a, b = rand_operand(M, K, 1, g), rand_operand(N, K, 0, g).t()
+    ah, al = split_bf16(a)
+    bh, bl = split_bf16(b)
     ch = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     cl = torch.empty_like(ch)
     gemm(Gemm(ah, bh, ch, a_lo=al, b_lo=bl, c_lo=cl))
     ref = a.double() @ b.double()
     torch.cuda.synchronize()
-    assert _rel(ch.double() + cl.double(), ref) < 2e-5
+    assert rel_err(ch.double() + cl.double(), ref) < 2e-5
     probs, refs = [], []
     for (M, N, K) in [(1024, 1568, 2560), (1024, 256, 2560), (512, 256, 2560)]:
-        x = _op(K, M, 1, g).t()          # mn-major A (dgates^T)
-        y = _op(N, K, 0, g).t()          # mn-major B (X)
-        xh, xl = _split(x)
-        yh, yl = _split(y)
+        x = rand_operand(K, M, 1, g).t()          # mn-major A (dgates^T)
+        y = rand_operand(N, K, 0, g).t()          # mn-major B (X)
+        xh, xl = split_bf16(x)
+        yh, yl = split_bf16(y)
         c = torch.zeros(M, N, device=DEV)
         probs.append(Gemm(xh, yh, c, a_lo=xl, b_lo=yl))
         refs.append(x.double() @ y.double())
@@ -80,7 +65,7 @@ def test_split_gemm_split_output_and_group():
         gemm_group(probs, splits, ws, tickets)
         torch.cuda.synchronize()
         for p, r in zip(probs, refs):
-            assert _rel(p.c, r) < 2e-5
+            assert rel_err(p.c, r) < 2e-5
 
 
 @pytest.mark.parametrize("splits", [[3, 3, 3, 1], [4, 2, 1, 2]])
@@ -94,10 +79,10 @@ def test_gemm_sp_item_orders_agree(splits):
     probs, refs = [], []
     for (M, N, K, ak) in [(1024, 1568, 2560, 0), (1024, 256, 2560, 0), (512, 256, 2560, 0),
                           (2560, 1568, 1024, 1)]:
-        x = _op(M, K, 1, g) if ak else _op(K, M, 1, g).t()
-        y = _op(N, K, 0, g).t().contiguous()
-        xh, xl = _split(x)
-        yh, yl = _split(y)
+        x = rand_operand(M, K, 1, g) if ak else rand_operand(K, M, 1, g).t()
+        y = rand_operand(N, K, 0, g).t().contiguous()
+        xh, xl = split_bf16(x)
+        yh, yl = split_bf16(y)
         probs.append(Gemm(xh, yh, torch.zeros(M, N, device=DEV), a_lo=xl, b_lo=yl))
         refs.append(x.double() @ y.double())
     k = kernels()
@@ -114,7 +99,7 @@ def test_gemm_sp_item_orders_agree(splits):
         k.r2_gemm5_set_mode(1)
     for a, b, r in zip(outs[1 | 64], outs[1], refs):
         assert torch.equal(a, b)
-        assert _rel(b, r) < 2e-5
+        assert rel_err(b, r) < 2e-5
 
 
 def _make(mode, B=16, preset="atari57", dtype="fp32", **kw):
@@ -189,7 +174,7 @@ def test_engine_fp32_matches_fp64_oracle(mode, preset, fused):
     lrel32 = abs(out32["loss"].item() - l64) / l64
     got = eng.layout.views(eng.grad)
     g32 = dict(on32.named_parameters())
-    errs = {n: (_rel(got[n].cpu(), p.grad), _rel(g32[n].grad, p.grad)) for n, p in online.named_parameters()}
+    errs = {n: (rel_err(got[n].cpu(), p.grad), rel_err(g32[n].grad, p.grad)) for n, p in online.named_parameters()}
     assert lrel < max(1e-4, 2 * lrel32), (lrel, lrel32)
     bad = {k: v for k, v in errs.items() if v[0] > max(1e-4, 2 * v[1])}
     assert not bad, errs
@@ -197,8 +182,8 @@ def test_engine_fp32_matches_fp64_oracle(mode, preset, fused):
     s = eng.starts.long()
     base = s - s % rp.cap_e
     rows = base[None] + (s[None] - base[None] + torch.arange(Lb, T, device=DEV)[:, None]) % rp.cap_e
-    p32 = _rel(out32["priority"], out["priority"])
-    assert _rel(rp.priority[rows].cpu(), out["priority"]) < max(1e-4, 2 * p32)
+    p32 = rel_err(out32["priority"], out["priority"])
+    assert rel_err(rp.priority[rows].cpu(), out["priority"]) < max(1e-4, 2 * p32)
     if preset == "dmlab30":     # the library convs inside the captured step
         eng.capture(warmup=1)
         for _ in range(3):
@@ -235,7 +220,7 @@ def test_engine_fp32_matches_fp64_oracle_at_bench_shape(bptt):
     assert lrel < max(1e-4, 2 * lrel32), (lrel, lrel32)
     got = eng.layout.views(eng.grad)
     g32 = dict(on32.named_parameters())
-    errs = {n: (_rel(got[n].cpu(), p.grad), _rel(g32[n].grad, p.grad)) for n, p in online.named_parameters()}
+    errs = {n: (rel_err(got[n].cpu(), p.grad), rel_err(g32[n].grad, p.grad)) for n, p in online.named_parameters()}
     assert len(errs) == 18
     bad = {k: v for k, v in errs.items() if v[0] > max(1e-4, 2 * v[1])}
     assert not bad, errs
@@ -243,8 +228,8 @@ def test_engine_fp32_matches_fp64_oracle_at_bench_shape(bptt):
     s = eng.starts.long()
     base = s - s % rp.cap_e
     rows = base[None] + (s[None] - base[None] + torch.arange(Lb, T, device=DEV)[:, None]) % rp.cap_e
-    p32 = _rel(out32["priority"], out["priority"])
-    assert _rel(rp.priority[rows].cpu(), out["priority"]) < max(1e-4, 2 * p32)
+    p32 = rel_err(out32["priority"], out["priority"])
+    assert rel_err(rp.priority[rows].cpu(), out["priority"]) < max(1e-4, 2 * p32)
     eng.capture(warmup=1)
     for _ in range(5):
         eng.step()
@@ -267,14 +252,14 @@ def test_engine_fp32_forward_activations():
     T, Lb = cfg.replay.seq_len, cfg.replay.burn_in
     with torch.no_grad():
         X = on.torso(obs.reshape(Tn * B, *obs.shape[2:]))
-        assert _rel(eng.X_on.cpu().double() + eng.X_on_lo.cpu().double(), X) < 2e-5
+        assert rel_err(eng.X_on.cpu().double() + eng.X_on_lo.cpu().double(), X) < 2e-5
         xp = X @ on.lstm.weight_ih.t() + on.lstm.bias_ih + on.lstm.bias_hh
-        assert _rel(eng.xp_on.cpu().double(), xp[:, eng.layout.gate_perm]) < 2e-5
+        assert rel_err(eng.xp_on.cpu().double(), xp[:, eng.layout.gate_perm]) < 2e-5
         hs, cs = on.lstm_seq(X.reshape(Tn, B, -1)[:T], b.h0.double(), b.c0.double())
         he = eng.hseq["on"].cpu().double() + eng.hseq_lo["on"].cpu().double()
-        assert _rel(he, hs) < 2e-5 and _rel(eng.cseq["on"].cpu().double(), cs) < 2e-5
+        assert rel_err(he, hs) < 2e-5 and rel_err(eng.cseq["on"].cpu().double(), cs) < 2e-5
         q = on.head(hs[Lb:]).reshape(-1, cfg.model.n_actions)
-        assert _rel(eng.q_on.cpu().double(), q) < 2e-5
+        assert rel_err(eng.q_on.cpu().double(), q) < 2e-5
 
 
 def test_engine_fp32_is_closer_to_oracle_than_bf16():
@@ -288,7 +273,7 @@ def test_engine_fp32_is_closer_to_oracle_than_bf16():
         torch.cuda.synchronize()
         online, out = _oracle64(rp, eng, net, tgt, cfg, "fixed")
         got = eng.layout.views(eng.grad)
-        res[dt] = max(_rel(got[n].cpu(), p.grad) for n, p in online.named_parameters())
+        res[dt] = max(rel_err(got[n].cpu(), p.grad) for n, p in online.named_parameters())
     assert res["fp32"] * 50 < res["bf16"], res
 
 
@@ -305,7 +290,7 @@ def test_engine_fp32_graph_step_and_seaquest_actions():
     on32, _ = _oracle(rp, eng, net, tgt, cfg, "fixed", torch.float32)
     got = eng.layout.views(eng.grad)
     g32 = dict(on32.named_parameters())
-    errs = {n: (_rel(got[n].cpu(), p.grad), _rel(g32[n].grad, p.grad)) for n, p in online.named_parameters()}
+    errs = {n: (rel_err(got[n].cpu(), p.grad), rel_err(g32[n].grad, p.grad)) for n, p in online.named_parameters()}
     assert all(e <= max(1e-4, 2 * e32) for e, e32 in errs.values()), errs
     cfg2, rp2, eng2, _, _ = _make("fixed", B=16)
     cfg3, rp3, eng3, _, _ = _make("fixed", B=16)
@@ -316,7 +301,7 @@ def test_engine_fp32_graph_step_and_seaquest_actions():
     eng3.step()
     torch.cuda.synchronize()
     assert torch.equal(rp2.step, rp3.step)
-    assert _rel(eng3.master, eng2.master) < 1e-6
+    assert rel_err(eng3.master, eng2.master) < 1e-6
     assert eng3.error_word() == 0
 
 
@@ -337,7 +322,7 @@ def test_torso_fwd_sp_matches_fp64():
     rows = [torch.randint(0, cap, (n,), dtype=torch.int32, device=dev, generator=g) for n in counts]
 
     def net():
-        w = [_split(torch.randn(32, kk, device=dev, generator=g) * 0.05) for kk in (256, 512, 288)]
+        w = [split_bf16(torch.randn(32, kk, device=dev, generator=g) * 0.05) for kk in (256, 512, 288)]
         b = [torch.randn(32, device=dev, generator=g) * 0.1 for _ in range(3)]
         return w, b
 
@@ -372,10 +357,10 @@ def test_torso_fwd_sp_matches_fp64():
         a2 = F.relu(F.conv2d(a1, W2, b[1].double(), stride=2))
         a3 = F.relu(F.conv2d(a2, W3, b[2].double(), stride=1))
         assert not (X == 7.0).any()
-        assert _rel(both(X), a3.reshape(a3.shape[0], -1)) < 2e-5
+        assert rel_err(both(X), a3.reshape(a3.shape[0], -1)) < 2e-5
         if s1 is not None:
-            assert _rel(both(s1), a1.permute(0, 2, 3, 1).reshape(-1, 400, 32)) < 2e-5
-            assert _rel(both(s2), a2.permute(0, 2, 3, 1).reshape(-1, 81, 32)) < 2e-5
+            assert rel_err(both(s1), a1.permute(0, 2, 3, 1).reshape(-1, 400, 32)) < 2e-5
+            assert rel_err(both(s2), a2.permute(0, 2, 3, 1).reshape(-1, 81, 32)) < 2e-5
 
 
 def test_td_fused_dh_matches_fp64_split():
@@ -389,7 +374,7 @@ def test_td_fused_dh_matches_fp64_split():
     N = eng.Ll * eng.B
     dz = eng.dz[:N].double() + eng.dz_lo[:N].double()
     w1 = eng.pk["head1"].double() + eng.pk_lo["head1"].double()
-    assert _rel(eng.dh[:N], dz @ w1) < 2e-5
+    assert rel_err(eng.dh[:N], dz @ w1) < 2e-5
 
 
 @pytest.mark.parametrize("fill", [0, -1])
@@ -407,7 +392,7 @@ def test_lstm_sp_tagged_word_handoff_over_launches(fill):
     g = torch.Generator(device=DEV).manual_seed(3)
     nwg = H // 16
     whh = torch.randn(nwg, 64, H, device=DEV, generator=g) * 0.06
-    wh, wl = _split(whh)
+    wh, wl = split_bf16(whh)
     c0 = torch.randn(B, H, device=DEV, generator=g) * 0.5
     h0 = torch.randn(B, H, device=DEV, generator=g) * 0.5
     err = torch.zeros(1, dtype=torch.int32, device=DEV)
@@ -449,5 +434,5 @@ def test_lstm_sp_tagged_word_handoff_over_launches(fill):
             c, h = c.reshape(B, H), h.reshape(B, H)
             for hs, hl, cs in b4:
                 h4 = hs[t].double() + hl[t].double()
-                assert _rel(h4, h) < 2e-5, t
-                assert _rel(cs[t], c) < 2e-5, t
+                assert rel_err(h4, h) < 2e-5, t
+                assert rel_err(cs[t], c) < 2e-5, t

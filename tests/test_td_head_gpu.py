@@ -9,12 +9,12 @@ the first bound.  Output buffers carry two extra rows; everything starts as NaN 
 
 With R2D2_TD_ORACLE_REPORT=<file> the measured errors are written there
 (profiles/td_oracle_errors.txt)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from gpu_support import DEV, NAN, dev, report_fixture, split_bf16
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
 from pytorch_r2d2_amd import td_ref
 from pytorch_r2d2_amd.ops._lib import kernels, ptr, stream_handle
 from test_td_ref_cpu import (ALPHA, BURN_IN, GAMMA_N, N_VALID, PRIO_EPS, SHAPES, VR_EPS, f32,
@@ -22,34 +22,20 @@ from test_td_ref_cpu import (ALPHA, BURN_IN, GAMMA_N, N_VALID, PRIO_EPS, SHAPES,
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-NAN = float("nan")
 BETA = f32(0.6)
 BF = torch.bfloat16
 # (entry point, split precision)
 ENTRIES = [("td_loss", False), ("td_duel", False), ("td_duel", True), ("td_duel_dh", False),
            ("td_duel_dh", True)]
 DUEL = ENTRIES[1:]
-_REPORT = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    path = os.environ.get("R2D2_TD_ORACLE_REPORT")
-    if path and _REPORT:
-        with open(path, "w") as f:
-            f.write("# max |delta - delta_float64| per case: the kernel, fp32 PyTorch (reference\n"
-                    "# formulation, CPU), and fp32 with h^-1's sqrt(1+v)-1 taken as v/(sqrt(1+v)+1)\n"
-                    "# (the last two only with value rescaling, vr = 1; 0 otherwise)\n"
-                    "# case                         vr beta entry            kernel     torch_fp32 "
-                    "alt_hinv_fp32\n")
-            for r in _REPORT:
-                f.write("%-30s %d  %.1f  %-16s %.3e  %.3e  %.3e\n" % r)
-
-
-def _dev(x):
-    return torch.as_tensor(np.ascontiguousarray(x)).to(DEV)
+_REPORT, _report = report_fixture(
+    "R2D2_TD_ORACLE_REPORT",
+    "# max |delta - delta_float64| per case: the kernel, fp32 PyTorch (reference\n"
+    "# formulation, CPU), and fp32 with h^-1's sqrt(1+v)-1 taken as v/(sqrt(1+v)+1)\n"
+    "# (the last two only with value rescaling, vr = 1; 0 otherwise)\n"
+    "# case                         vr beta entry            kernel     torch_fp32 "
+    "alt_hinv_fp32\n",
+    fmt="%-30s %d  %.1f  %-16s %.3e  %.3e  %.3e")
 
 
 def _poison(*shape, dtype=torch.float32, fill=NAN):
@@ -65,16 +51,10 @@ def _np(t, rows=None):
     return t.detach().float().cpu().numpy().astype(np.float64)
 
 
-def _split(x):
-    """hi / lo bf16 planes of an fp32 tensor (csrc/split.h)."""
-    hi = x.to(BF)
-    return hi, (x - hi.float()).to(BF)
-
-
 def _stage(c):
     """Device copies of a case's inputs (once per case)."""
     if "dev" not in c:
-        c["dev"] = {k: _dev(np.asarray(c[k], dtype=np.float32) if k.startswith("q_") else c[k])
+        c["dev"] = {k: dev(np.asarray(c[k], dtype=np.float32) if k.startswith("q_") else c[k])
                     for k in ("q_sa", "q_arg", "q_tgt", "starts", "probs", "action", "reward", "done")}
         c["dev"]["n_valid"] = torch.tensor([N_VALID], dtype=torch.int32, device=DEV)
     return c["dev"]
@@ -91,7 +71,7 @@ def make_head(c, HD, H=256):
         zr32 = torch.relu(torch.randn(n, 2 * HD, generator=g))
         w2 = torch.randn(1 + A, HD, generator=g)
         w1t = torch.randn(H, 2 * HD, generator=g) / float(np.sqrt(2 * HD))
-        hi, lo = _split(w1t)
+        hi, lo = split_bf16(w1t)
         c[key] = dict(HD=HD, zr_bf=zr32.to(BF).to(DEV), zr_f32=zr32.to(DEV), w2=w2.to(DEV),
                       w1t=hi.to(DEV), w1t_lo=lo.to(DEV))
         frac = float((zr32 == 0).float().mean())
@@ -117,7 +97,7 @@ def _launch(entry, c, vr, beta, *, sp=False, head=None, dp=None, probs=True, fus
     if fwd is not None:       # the Q rows are outputs of the launch
         q = [_poison(n + 2, A) for _ in range(3)]
         o["q_on"], o["q_nx"], o["q_tg"] = q
-    dpt = _dev(np.asarray(dp, dtype=np.float32)) if dp is not None else None
+    dpt = dev(np.asarray(dp, dtype=np.float32)) if dp is not None else None
     targs = (ptr(q[0]), ptr(q[1]), ptr(q[2]), ptr(d["starts"]), ptr(d["probs"]) if probs else 0,
              ptr(d["action"]), ptr(d["reward"]), ptr(d["done"]), ptr(o["dq"]), ptr(o["loss"]),
              ptr(o["td_abs"]), ptr(o["priority"]), ptr(o["is_w"]), ptr(d["n_valid"]), Tl, B, A,

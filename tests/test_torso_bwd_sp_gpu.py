@@ -11,16 +11,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_support import rel_err
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 CAP = 8
 NAMES = ["vis_layers.0.weight", "vis_layers.0.bias", "vis_layers.2.weight", "vis_layers.2.bias",
          "vis_layers.4.weight", "vis_layers.4.bias"]
-
-
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
 
 
 def _split(x):
@@ -105,7 +102,7 @@ def test_torso_bwd_sp_matches_fp64_autograd(world, n, grid):
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert torch.isfinite(outs[0][0]).all()
     got = L.views(outs[0][1])
-    errs = {name: (_rel(got[name], r), _rel(r3, r)) for name, r, r3 in zip(NAMES, ref, r32)}
+    errs = {name: (rel_err(got[name], r), rel_err(r3, r)) for name, r, r3 in zip(NAMES, ref, r32)}
     print(f"n={n} grid={grid} (kernel, fp32 torch) rel err vs float64: {errs}")
     bad = {k_: v for k_, v in errs.items() if v[0] > max(1e-4, 2 * v[1])}
     assert not bad, errs

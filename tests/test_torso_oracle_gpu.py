@@ -9,13 +9,14 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import DEV, Guarded, dev, dev_bf16
+from gpu_support import stop_after_a_gpu_error  # noqa: F401
+from pytorch_r2d2_amd import refnum as rn
 from pytorch_r2d2_amd import torso_ref as R
 from pytorch_r2d2_amd.ops._lib import kernels, ptr, stream_handle
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 PAD = 1024                     # guard elements at each end of an output buffer
-NAN = float("nan")
 FWD = {c["name"]: c for c in R.FWD_CASES}
 BWD = {c["name"]: c for c in R.BWD_CASES}
 SP = {c["name"]: c for c in R.SP_CASES}
@@ -26,43 +27,8 @@ def _fig(line):
     print("torso-oracle: " + line)
 
 
-class Guarded:
-    """An output buffer between two guard bands, all NaN poison before the launch."""
-
-    def __init__(self, shape, dtype=torch.float32, pad=PAD):
-        self.shape, self.pad = tuple(shape), (pad + 7) // 8 * 8
-        self.n = int(np.prod(self.shape))
-        self.full = torch.full((self.n + 2 * self.pad,), NAN, dtype=dtype, device=DEV)
-        self.body = self.full[self.pad:self.pad + self.n]
-
-    def ptr(self):     # (an empty body still has an address)
-        return self.full.data_ptr() + self.pad * self.full.element_size()
-
-    def host_full(self):
-        return self.full.float().cpu().numpy()
-
-    def host(self):
-        return self.body.float().cpu().numpy().reshape(self.shape)
-
-    def bits(self):
-        if self.full.dtype == torch.bfloat16:
-            return self.body.view(torch.int16).cpu().numpy().view(np.uint16).reshape(self.shape)
-        return self.body.view(torch.int32).cpu().numpy().view(np.uint32).reshape(self.shape)
-
-    def owned(self, label, name, valid=None):
-        R.check_ownership(label, name, self.host_full(), self.pad, valid)
-
-    def untouched(self, label, name):
-        R.check_untouched(label, name, self.host_full())
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _dev_bf16(a):
-    """fp32 values that are exact in bf16 -> a bf16 tensor with those bits."""
-    return _dev(R.bf16_bits(a).view(np.int16)).view(torch.bfloat16)
+def _guarded(shape, dtype=torch.float32, pad=PAD):
+    return Guarded(shape, dtype, pad)
 
 
 _WTS = {}
@@ -70,8 +36,8 @@ _WTS = {}
 
 def _dev_weights(geo, wts, key):
     if key not in _WTS:
-        _WTS[key] = [_dev_bf16(wts["w1_pk"]), _dev(wts["b1"]), _dev_bf16(wts["w2_pk"]), _dev(wts["b2"]),
-                     _dev_bf16(wts["w3_pk"]), _dev(wts["b3"])]
+        _WTS[key] = [dev_bf16(wts["w1_pk"]), dev(wts["b1"]), dev_bf16(wts["w2_pk"]), dev(wts["b2"]),
+                     dev_bf16(wts["w3_pk"]), dev(wts["b3"])]
     return _WTS[key]
 
 
@@ -82,16 +48,16 @@ class FwdRun:
 
     def __init__(self, geo, ops, saves=None, null_rows=None):
         self.geo, self.ops = geo, ops
-        self.store = _dev(ops["store"])
+        self.store = dev(ops["store"])
         self.keep, self.outs, words = [], [], []
         for i, job in enumerate(ops["jobs"]):
             n = job["n"]
-            rows = None if job["rows"] is None or null_rows else _dev(job["rows"])
+            rows = None if job["rows"] is None or null_rows else dev(job["rows"])
             w = _dev_weights(geo, job["wts"], (geo.key, job["wts"]["seed"]))
             sv = job["saves"] if saves is None else saves
-            o = dict(out=Guarded((n, 32, geo.P3), torch.bfloat16),
-                     save1=Guarded((n, geo.P1, 32), torch.bfloat16) if sv else None,
-                     save2=Guarded((n, geo.P2, 32), torch.bfloat16) if sv else None)
+            o = dict(out=_guarded((n, 32, geo.P3), torch.bfloat16),
+                     save1=_guarded((n, geo.P1, 32), torch.bfloat16) if sv else None,
+                     save2=_guarded((n, geo.P2, 32), torch.bfloat16) if sv else None)
             words += [ptr(rows), n] + [ptr(t) for t in w] + [
                 o["out"].ptr(), o["save1"].ptr() if sv else 0, o["save2"].ptr() if sv else 0, 0]
             self.keep += [rows, job["wts"]]
@@ -219,9 +185,9 @@ SP_OUT = ("out", "out_lo", "s1", "s1_lo", "s2", "s2_lo")
 def _dev_weights_sp(geo, wts):
     key = ("sp", geo.key, wts["seed"])
     if key not in _WTS:
-        _WTS[key] = [_dev_bf16(wts["w1_hi"]), _dev_bf16(wts["w1_lo"]), _dev(wts["b1"]),
-                     _dev_bf16(wts["w2_hi"]), _dev_bf16(wts["w2_lo"]), _dev(wts["b2"]),
-                     _dev_bf16(wts["w3_hi"]), _dev_bf16(wts["w3_lo"]), _dev(wts["b3"])]
+        _WTS[key] = [dev_bf16(wts["w1_hi"]), dev_bf16(wts["w1_lo"]), dev(wts["b1"]),
+                     dev_bf16(wts["w2_hi"]), dev_bf16(wts["w2_lo"]), dev(wts["b2"]),
+                     dev_bf16(wts["w3_hi"]), dev_bf16(wts["w3_lo"]), dev(wts["b3"])]
     return _WTS[key]
 
 
@@ -230,14 +196,14 @@ class SpRun:
 
     def __init__(self, geo, ops, saves=None, null_rows=None):
         self.geo, self.ops = geo, ops
-        self.store = _dev(ops["store"])
+        self.store = dev(ops["store"])
         self.keep, self.outs, words = [], [], []
         for job in ops["jobs"]:
             n = job["n"]
-            rows = None if job["rows"] is None or null_rows else _dev(job["rows"])
+            rows = None if job["rows"] is None or null_rows else dev(job["rows"])
             sv = job["saves"] if saves is None else saves
             shapes = dict(out=(n, 32, geo.P3), s1=(n, geo.P1, 32), s2=(n, geo.P2, 32))
-            o = {k: Guarded(shapes[k.split("_")[0]], torch.bfloat16) if sv or k.startswith("out") else None
+            o = {k: _guarded(shapes[k.split("_")[0]], torch.bfloat16) if sv or k.startswith("out") else None
                  for k in SP_OUT}
             words += [ptr(rows), n] + [ptr(t) for t in _dev_weights_sp(geo, job["wts"])] + [
                 o[k].ptr() if o[k] is not None else 0 for k in SP_OUT] + [0, 0, 0]
@@ -289,8 +255,8 @@ def test_split_forward_case(name):
     assert run.launch(case["grid"]) == 0
     for j, job, stored in run.check(name, strides):
         if case["jobs"][j].get("w1") == "zero":
-            hi, lo = R.split_planes(np.maximum(job["wts"]["b1"], 0))
-            assert (R.bf16_val(stored["s1"]) == hi).all() and (R.bf16_val(stored["s1_lo"]) == lo).all()
+            hi, lo = rn.split_planes(np.maximum(job["wts"]["b1"], 0))
+            assert (rn.bf16_val(stored["s1"]) == hi).all() and (rn.bf16_val(stored["s1_lo"]) == lo).all()
     if not all(j["saves"] for j in ops["jobs"]):
         full = SpRun(geo, ops, saves=True)
         assert full.launch(case["grid"]) == 0
@@ -365,13 +331,13 @@ class BwdRun:
         o, self.geo = self.ops, self.ops["geo"]
         n = case["n"]
         self.G = R.effective_grid(case["grid"], n)
-        self.t = dict(store=_dev(o["store"]), rows=_dev(o["rows"]), act1=_dev_bf16(o["act1"]),
-                      act2=_dev_bf16(o["act2"]), dx3=_dev_bf16(o["dx3"]), out3=_dev_bf16(o["out3"]),
-                      w3dg=_dev_bf16(o["w3_dg"]), w2dg=_dev_bf16(o["w2_dg"]), dst=_dev(o["dst"]),
-                      scale=_dev(o["scale"]))
+        self.t = dict(store=dev(o["store"]), rows=dev(o["rows"]), act1=dev_bf16(o["act1"]),
+                      act2=dev_bf16(o["act2"]), dx3=dev_bf16(o["dx3"]), out3=dev_bf16(o["out3"]),
+                      w3dg=dev_bf16(o["w3_dg"]), w2dg=dev_bf16(o["w2_dg"]), dst=dev(o["dst"]),
+                      scale=dev(o["scale"]))
         self.slab_rows = max(case["grid"], n) + 1
-        self.slab = Guarded((self.slab_rows, self.geo.SLAB))
-        self.grad = Guarded((o["grad_numel"],))
+        self.slab = _guarded((self.slab_rows, self.geo.SLAB))
+        self.grad = _guarded((o["grad_numel"],))
 
     def args(self, **over):
         t, o = self.t, self.ops
@@ -445,15 +411,15 @@ class SpBwdRun(BwdRun):
         o, self.geo = self.ops, self.ops["geo"]
         n = case["n"]
         self.G = R.effective_grid(case["grid"], n)
-        self.t = dict(store=_dev(o["store"]), rows=_dev(o["rows"]), out3=_dev_bf16(o["out3"]),
-                      dst=_dev(o["dst"]), scale=_dev(o["scale"]))
+        self.t = dict(store=dev(o["store"]), rows=dev(o["rows"]), out3=dev_bf16(o["out3"]),
+                      dst=dev(o["dst"]), scale=dev(o["scale"]))
         for k in ("act1", "act2", "dx3"):
-            self.t[k], self.t[k + "l"] = _dev_bf16(o[k + "_hi"]), _dev_bf16(o[k + "_lo"])
+            self.t[k], self.t[k + "l"] = dev_bf16(o[k + "_hi"]), dev_bf16(o[k + "_lo"])
         for k in ("w3", "w2"):
-            self.t[k + "dg"], self.t[k + "dgl"] = _dev_bf16(o[k + "_dg"]), _dev_bf16(o[k + "_dg_lo"])
+            self.t[k + "dg"], self.t[k + "dgl"] = dev_bf16(o[k + "_dg"]), dev_bf16(o[k + "_dg_lo"])
         self.slab_rows = max(case["grid"], n) + 1
-        self.slab = Guarded((self.slab_rows, self.geo.SLAB))
-        self.grad = Guarded((o["grad_numel"],))
+        self.slab = _guarded((self.slab_rows, self.geo.SLAB))
+        self.grad = _guarded((o["grad_numel"],))
 
     def launch(self, **over):
         t = self.t
@@ -508,7 +474,7 @@ def test_split_backward_refusals_write_nothing():
 
 def _frames_ref(fr):
     """bf16(fl32(u8) * fl32(1/255)): one rounding per element."""
-    return R.bf16_bits((fr.astype(np.float32) * np.float32(1.0 / 255.0)).astype(np.float32))
+    return rn.bf16_bits((fr.astype(np.float32) * np.float32(1.0 / 255.0)).astype(np.float32))
 
 
 @pytest.mark.parametrize("rows_mode", ["dup_desc", "null"])
@@ -520,14 +486,14 @@ def test_frames_to_bf16_bit_exact(nhwc, rows_mode):
     rows = R.make_rows("helpers", n, 6, rows_mode)
     fr = R.gather(geo, store, rows, n)
     want = _frames_ref(fr.transpose(0, 2, 3, 1) if nhwc else fr).reshape(n, geo.fb)
-    out = Guarded((n, geo.fb), torch.bfloat16)
-    s, r = _dev(store), (None if rows is None else _dev(rows))
+    out = _guarded((n, geo.fb), torch.bfloat16)
+    s, r = dev(store), (None if rows is None else dev(rows))
     fn = kernels().r2_frames_to_bf16_nhwc if nhwc else kernels().r2_frames_to_bf16
     assert fn(ptr(s), ptr(r), n, out.ptr(), stream_handle()) == 0
     torch.cuda.synchronize()
     out.owned("frames_to_bf16", "out")
     assert np.array_equal(out.bits(), want)
-    idle = Guarded((n, geo.fb), torch.bfloat16)
+    idle = _guarded((n, geo.fb), torch.bfloat16)
     assert fn(ptr(s), ptr(r), 0, idle.ptr(), stream_handle()) == 0
     torch.cuda.synchronize()
     idle.untouched("frames_to_bf16 n=0", "out")
@@ -537,19 +503,19 @@ def test_bias_relu_nhwc_bit_exact_and_refusals():
     """In place on a guarded buffer, C = 32, a length whose last block is partial (n / 8 = 308)."""
     Cc, n = 32, 32 * 77
     r = np.random.default_rng(3)
-    x = R.bf16_round(r.standard_normal(n))
+    x = rn.bf16_round(r.standard_normal(n))
     x[:8] = [0.0, -0.0, 1.0, -1.0, 2.0 ** -126, -2.0 ** -126, 3.0, -3.0]
     bias = r.standard_normal(Cc).astype(np.float32)
     bias[1] = 0.0
-    want = R.bf16_bits(np.maximum((x.reshape(-1, Cc) + bias).astype(np.float32), np.float32(0))).reshape(-1)
-    buf = Guarded((n,), torch.bfloat16)
-    buf.body.copy_(_dev_bf16(x))
-    b = _dev(bias)
+    want = rn.bf16_bits(np.maximum((x.reshape(-1, Cc) + bias).astype(np.float32), np.float32(0))).reshape(-1)
+    buf = _guarded((n,), torch.bfloat16)
+    buf.body.copy_(dev_bf16(x))
+    b = dev(bias)
     k = kernels()
     for bad in ((buf.ptr(), 12, 24), (buf.ptr(), Cc, n - 8), (buf.ptr() + 8, Cc, n)):   # C % 8, n % C, alignment
         assert k.r2_bias_relu_nhwc_bf16(bad[0], ptr(b), bad[1], bad[2], stream_handle()) == -1
     torch.cuda.synchronize()
-    assert np.array_equal(buf.bits(), R.bf16_bits(x)), "a refused launch wrote"
+    assert np.array_equal(buf.bits(), rn.bf16_bits(x)), "a refused launch wrote"
     assert k.r2_bias_relu_nhwc_bf16(buf.ptr(), ptr(b), Cc, n, stream_handle()) == 0
     torch.cuda.synchronize()
     buf.owned("bias_relu", "x")
@@ -562,13 +528,13 @@ def test_relu_mask_bit_exact_and_refusals():
     """n = 8 k with k odd (333), so the last vector of the last block is the tail."""
     n = 8 * 333
     r = np.random.default_rng(4)
-    g = R.bf16_round(r.standard_normal(n))
-    act = R.bf16_round(r.standard_normal(n)) * (r.random(n) < 0.7)
+    g = rn.bf16_round(r.standard_normal(n))
+    act = rn.bf16_round(r.standard_normal(n)) * (r.random(n) < 0.7)
     act[:4] = [0.0, -0.0, 2.0 ** -126, -2.0 ** -126]
-    gb = R.bf16_bits(g)
+    gb = rn.bf16_bits(g)
     want = np.where(act > 0, gb, np.uint16(0))
-    gd, ad = _dev_bf16(g), _dev_bf16(act)
-    out = Guarded((n,), torch.bfloat16)
+    gd, ad = dev_bf16(g), dev_bf16(act)
+    out = _guarded((n,), torch.bfloat16)
     k = kernels()
     assert k.r2_relu_mask_bf16(ptr(gd), ptr(ad), out.ptr(), n - 4, stream_handle()) == -1     # n % 8
     for i in range(3):                                                                        # alignment

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from pytorch_r2d2_amd import refnum as rn
 from pytorch_r2d2_amd import torso_ref as R
 from pytorch_r2d2_amd.config import get_config
 from pytorch_r2d2_amd.engine.layout import ParamLayout
@@ -136,7 +137,7 @@ def test_forward_emulation_within_bounds(name):
             continue
         uses = R.check_forward(f"{name}/job{j}", ops["geo"], job["frames"], job["wts"], out, strides[j])
         for k in ("save1", "save2", "out"):
-            R.check_ownership(name, k, R.guarded_image(out[k], PAD), PAD)
+            rn.check_ownership(name, k, R.guarded_image(out[k], PAD), PAD)
         print(f"torso-oracle: fwd {name}/job{j} " + " ".join(f"{k} {v:.3f}" for k, v in uses.items()))
         assert max(uses.values()) <= 1.0
 
@@ -160,8 +161,8 @@ def test_split_forward_emulation_within_bounds(name):
         print(f"torso-oracle: fwd {name}/job{j} " + " ".join(f"{k} {v:.3f}" for k, v in uses.items()))
         assert max(uses.values()) <= 1.0
         if SP[name]["jobs"][j].get("w1") == "zero":       # act1 = ReLU(b1) exactly, lo plane included
-            hi, lo = R.split_planes(np.maximum(job["wts"]["b1"], 0))
-            assert (R.bf16_val(out["s1"]) == hi).all() and (R.bf16_val(out["s1_lo"]) == lo).all()
+            hi, lo = rn.split_planes(np.maximum(job["wts"]["b1"], 0))
+            assert (rn.bf16_val(out["s1"]) == hi).all() and (rn.bf16_val(out["s1_lo"]) == lo).all()
 
 
 def test_digit_quantisation_error_is_at_most_s_over_32768():
@@ -182,7 +183,7 @@ def test_backward_emulation_within_bounds(name):
     u_grad = R.check_reduce(name, slab, ops["dst"], ops["scale"], grad)
     torso = np.zeros(grad.size, bool)
     torso[ops["dst"]] = True
-    R.check_ownership(name, "grad", grad, 0, valid=torso)
+    rn.check_ownership(name, "grad", grad, 0, valid=torso)
     print(f"torso-oracle: bwd {name} slab {u_slab:.3f} grad {u_grad:.3f}")
     assert u_slab <= 1.0 and u_grad <= 1.0
 
@@ -241,7 +242,7 @@ def test_forward_mutation_rejected(mutation):
                 continue
             if mutation == "pad_lanes_written":     # the padded lanes of conv1's last pixel tile stored
                 spill = (-ops["geo"].P1) % 32 * 32
-                hit = _rejects(lambda: R.check_ownership(name, "save1", R.guarded_image(out["save1"], PAD, spill), PAD))
+                hit = _rejects(lambda: rn.check_ownership(name, "save1", R.guarded_image(out["save1"], PAD, spill), PAD))
             else:
                 hit = _rejects(lambda: R.check_forward(name, ops["geo"], job["frames"], job["wts"], out,
                                                        strides[j], mutation))
@@ -261,7 +262,7 @@ def test_split_forward_mutation_rejected(mutation):
             if mutation == "pad_lanes_written":
                 spill = (-ops["geo"].P1) % 32 * 32
                 for k in ("s1", "s1_lo"):
-                    hit |= _rejects(lambda: R.check_ownership(name, k, R.guarded_image(out[k], PAD, spill), PAD))
+                    hit |= _rejects(lambda: rn.check_ownership(name, k, R.guarded_image(out[k], PAD, spill), PAD))
             else:
                 hit |= _rejects(lambda: R.check_forward_sp(name, ops["geo"], job["frames"], job["wts"], out,
                                                            strides[j], mutation))
