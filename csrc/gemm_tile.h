@@ -371,7 +371,7 @@ __device__ __forceinline__ void g2s_tile_acc(const GemmProb& P, int tm, int tn, 
   __builtin_amdgcn_s_barrier();            // every wave done reading the ring (epilogue reuses it)
 }
 
-// Host: parse one 16 x int64 problem descriptor (ops/gemm.py Gemm.desc layout) and check the
+// Host: parse one GEMM_DESC (20) x int64 problem descriptor (ops/gemm.py Gemm.desc layout) and check the
 // shape rules of the 128x128 paths.  0 = ok.
 static inline int gemm_parse_desc(const int64_t* d, GemmProb& p) {
   p.A = (const bf16*)d[0]; p.B = (const bf16*)d[1]; p.C = (void*)d[2];

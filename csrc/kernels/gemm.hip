@@ -634,7 +634,7 @@ __global__ __launch_bounds__(256) void gemm_group_kernel(const GroupArgs a) {
   g2_epilogue_lds(P, tm * g2::BM, tn * g2::BN, wm, wn, lane, acc, lds);
 }
 
-// descs: np x 16 int64 (ops/gemm.py layout); split[i] >= 1; ws: sum over split problems of
+// descs: np x GEMM_DESC int64 (ops/gemm.py layout); split[i] >= 1; ws: sum over split problems of
 // tiles * split * 64 KB; tickets: one per tile of split problems, zero at first use.
 extern "C" long long r2_gemm_group_ws_bytes(const int64_t* descs, const int* split, int np) {
   long long b = 0;

@@ -6,7 +6,9 @@
 // K loop.  Here every K tile stages A_hi, A_lo, B_hi, B_lo once (2x the bf16 traffic) and each
 // fragment pair feeds three MFMAs (lo.hi, hi.lo, hi.hi, small terms first) -- the same
 // arithmetic as split.h mfma16_x3 -- so the MFMA pipe, not the operand path, sets the pace.
-// A plane that is null (an operand exact in bf16) is neither staged nor multiplied.
+// Both operands of every problem must come with their lo plane: r2_gemm5 refuses a problem without
+// A_lo or B_lo (-10).  An operand that is exact in bf16 goes through the multi-pass route of
+// r2_gemm (gemm.hip), which skips the pass of a null plane.
 //
 // Tile BM x BN x 64 (BM in {128, 192, 256}, BN in {64, 128}), 8 waves = 2 (M) x 4 (N), wave
 // (BM/2) x (BN/4) as (BM/32) x (BN/64) v_mfma_f32_16x16x32_bf16 accumulators, two waves per
