@@ -160,7 +160,7 @@ class LearnerConfig:
     bptt_dh: bool = True
     # (round 5's post-BPTT GEMMs on the BPTT launch's idle workgroups -- learner.bptt_gemms --
     # slowed the recurrence in every arm and were removed: profiles/r05_bptt_helpers_roles.txt)
-    # Single-rank split-precision step, software-pipelined over two steps (learner_engine.py
+    # Single-rank split-precision step, software-pipelined over two steps (step_driver.py
     # "hoisted step"): right after step k's TD launch a side stream runs step k's priority tail,
     # step k+1's sample and step k+1's target-network torso frames on the CUs the BPTT leaves
     # free (a frame queue the next step's torso launch finishes); bit-identical to the plain step

@@ -30,7 +30,10 @@ priority scatters.  Here a step is:
               the levels; the 3-launch form when the grid cannot be resident)
 
 No host synchronisation happens inside a step, so the whole step (minus collectives) is
-captured once into a HIP graph and replayed.
+captured once into a HIP graph and replayed.  This module is what a step computes (the kernel
+sequence above, its buffers, weight packs, checkpoints, diagnostics); how it is issued -- eager, one
+graph, DP segment graphs, the one-graph DP step, the hoisted step's variants, the multi-step chunk
+graph -- is ``step_driver.StepDrivers``, which ``LearnerEngine`` inherits.
 
 target_mode (config.learner.target_mode):
   shifted   -- R2D2 paper: one online and one target chain over T+n frames from the stored
@@ -59,32 +62,7 @@ from ..ops.torso_lib import (fused_torso_fwd_geom, fused_torso_supported, gather
                              torso_forward_library_sp, torso_fwd_fused)
 from .layout import ParamLayout, UNITS
 from .replay_hbm import HBMReplay
-
-
-def _graph_upload(g) -> None:
-    """Upload an instantiated graph's executable to the device (hipGraphUpload on the current
-    stream), so its first replay -- possibly inside a timed loop -- does not pay for it.  Best
-    effort: without the runtime entry point the first replay uploads as before."""
-    import os
-    try:
-        exec_h = int(g.raw_cuda_graph_exec())
-        lib = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
-        lib.hipGraphUpload.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        lib.hipGraphUpload(ctypes.c_void_p(exec_h), ctypes.c_void_p(stream_handle()))
-    except (AttributeError, OSError, RuntimeError):
-        pass
-
-
-def _dispatch_serialized() -> bool:
-    """True when kernel dispatches run one at a time (rocprofv3 counter collection / thread trace,
-    AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING).  The hoisted step's early fork has a kernel on the
-    side queue wait on the device for the TD kernel of the main queue, which a serialised
-    dispatcher never runs beside it (a bounded stall and an error word), so it forks after TD there."""
-    import os
-    env = os.environ
-    on = lambda k: env.get(k, "0").strip().lower() not in ("", "0", "false", "no", "off")  # noqa: E731
-    return (on("ROCPROF_COUNTER_COLLECTION") or on("ROCPROF_ADVANCED_THREAD_TRACE")
-            or on("HIP_LAUNCH_BLOCKING") or env.get("AMD_SERIALIZE_KERNEL", "0") not in ("", "0"))
+from .step_driver import StepDrivers, _dispatch_serialized, _graph_upload, dp_hoist_plan  # noqa: F401
 
 
 def device_cus(device) -> int:
@@ -111,25 +89,7 @@ def torso_bwd_grid(n_frames: int, reserve_cus: int = 0, n_cus: int = 256) -> int
     return -(-n_frames // per)
 
 
-def dp_hoist_plan(dp_global: bool, inm: str):
-    """The hoisted data-parallel step (dist.hoist_dp) as ("segment" | "collective", name) pairs in
-    issue order.  ``inm``: 'P' = the step samples at its start, 'H' = the previous step's side
-    branch sampled.  The collective subsequence depends on neither ``inm`` nor on whether the side
-    branch runs target frames (that is inside "core_side"): ranks decide 'P' / 'H' on their own
-    replay and must still meet at every collective.  The side branch (priority tail, counter, next
-    sample + shard stats, target frames) forks and joins inside "core_side" and holds no collective;
-    there is no priority segment."""
-    if inm not in ("P", "H"):
-        raise ValueError("inm must be 'P' or 'H'")
-    plan = [("segment", "sample")] if inm == "P" else []
-    if dp_global:
-        plan.append(("collective", "all_gather"))        # beside fwd_head, joined before core_side
-    plan += [("segment", "fwd_head"), ("segment", "core_side"), ("collective", "all_reduce_core"),
-             ("segment", "torso"), ("collective", "all_reduce_torso"), ("segment", "update")]
-    return plan
-
-
-class LearnerEngine:
+class LearnerEngine(StepDrivers):
     def _comm_reserve(self) -> int:
         dc = self.cfg.dist
         if self.dp and dc.overlap_allreduce and self.device.type == "cuda":
@@ -225,6 +185,24 @@ class LearnerEngine:
         self._dh_done = False         # ... and the dh = dz @ W1 product (learner.td_fuse_dh)
         self.graph = None
         self.stats: Dict[str, float] = {}
+        # ---- host-side state that the step drivers (step_driver.py) and the phases read, each name
+        # with its writer (``_alloc`` adds hoist, hoisted_steps, writes_covered, _cover, _sets, _cur)
+        self._hoist_ready = False     # _hoist_step: the previous step sampled the next batch
+        self._hoist_gen = self._hoist_unc = self._hoist_t = None   # _note_presample: the replay then
+        self._hoist_due = False       # the hoisted bodies: this step's update syncs the target
+        self._dev_step_off = None     # _hoist_step: device step counter - steps_done (None: read it)
+        self._side = self._gather_stream = None     # _side_stream / _gather_fork, on first use
+        self._early_fork = self._early_post = None  # _hoist_td_side / _forward_tail: the early fork's events
+        self._early_refused = False   # _hoist_side: the fused tail cannot wait for TD on the device
+        self._hgraphs, self._hsegs, self._one_graphs = {}, {}, {}   # capture / _capture_one_dp, by variant
+        self._cgraph = self._one_graph = None       # capture (the chunk graph) / _capture_one_dp
+        self._one_dp_graph = False    # _capture_one_dp: the one-graph DP step exists
+        self.graphs, self._seg_replays = [], []     # capture: the step's graph, or the DP segments'
+        self.chunks_run = 0           # run_steps: chunk graph replays
+        self._rollout = self._gsync = None          # _make_rollout (capture, DP) / _sync, on first use
+        self._pack_deferred = None    # _pack_step -> _priorities: the repack rides on the priority tail
+        self._torso_deferred = False  # _backward_torso -> _update: the torso slabs are not summed yet
+        self._hprev_sp = self.gg_ws = None          # _post_bptt_jobs / _group_splits, on first use
         self._alloc()
         # world 1 (no gradient all-reduce): the torso backward's slab reduction rides on the
         # optimizer launch (r2_rmsprop_pack_slab / r2_adam_pack_slab: one launch fewer); the torso
@@ -463,147 +441,6 @@ class LearnerEngine:
         return (self.cfg.learner.fuse_pack_tail and not self.dp and self.device.type == "cuda"
                 and self.cfg.replay.fused_prio_tail and not self.hoist)
 
-    # ------------------------------------------------------------------ hoisted step
-    # Split-precision step software-pipelined over two steps: single rank, and (opt-in,
-    # dist.hoist_dp: "the hoisted step on data-parallel ranks" below) DP ranks (round-6 verdict item
-    # 1; reference: the serial /root/reference/learner.py:68-110).  Step k's priority tail needs
-    # only its TD errors and step k+1's sample only the repaired tree, so right after the TD
-    # launch a side stream runs [priority tail(k) + step counter, sample(k+1) into the other
-    # sample set, target-net torso(k+1) frames from a queue] while the main stream runs the
-    # BPTT and the rest of step k.  The side torso runs on the CUs the BPTT leaves free and stops
-    # taking frames when the BPTT raises its stop word; step k+1's torso launch takes the rest of
-    # the queue.  Every frame is computed by the same kernel code from the same operands, the
-    # sample uses the same device step counter, and the target packs are only used when no
-    # target sync happened in between (the host knows the sync steps: the update is captured with
-    # the due decision baked in), so the step is bit-identical to the plain one -- as long as the
-    # replay does not change between the hoisted sample and the step that trains on it.  A batch
-    # sampled before a replay write is dropped (_hoist_fresh: HBMReplay.total_written moved), and
-    # that step samples at its start like the plain one; only a driver that keeps its writes away
-    # from pending batches (engine/concurrent.py) sets ``writes_covered``.  ``cover_writes`` keeps
-    # the batch across the steps of a serial actor that clears its starts ahead of its write head.
-    # Every optimizer setting hoists: the side branch's tail advances the device step counter
-    # before the update runs (the join precedes it), so Adam's step count is the counter itself
-    # there and counter + 1 in the plain step (``_step_off``, the same reason as
-    # ``_baked_interval``); the clip norm (r2_grad_sumsq) is a fixed-order sum, the same bits in
-    # both step shapes.
-    # Data-parallel ranks hoist only with dist.hoist_dp (default off: the serial DP step, the same
-    # graphs, kernels and bits as before the knob existed); no N > 1 RCCL run has exercised it.
-    def _hoist_ok(self) -> bool:
-        lc = self.cfg.learner
-        return bool(lc.hoist and self.sp and self.fused_torso and not self.sp_lib
-                    and self.device.type == "cuda"
-                    and (not self.dp or self.cfg.dist.hoist_dp)
-                    and self.row_dst4 is not None and self.cfg.replay.fused_prio_tail
-                    and not lc.zero_stored_state)
-
-    def _use_set(self, i: int) -> None:
-        self._cur = i
-        S = self._sets[i]
-        self.starts, self.probs, self.rows = S["starts"], S["probs"], S["rows"]
-        self.h0, self.c0 = S["h0"], S["c0"]
-        self.dp_send = S["dp_send"]
-
-    def invalidate_hoist(self) -> None:
-        """Drop the batch the previous step sampled (and the target frames it computed) for the
-        next one: call after changing the weights between steps, or the replay through a path
-        that does not count its rows in ``HBMReplay.total_written`` (the counted writers -- actor
-        steps, ingests -- are noticed by ``_hoist_fresh``).  The next step samples at its start,
-        as the plain step does."""
-        self._hoist_ready = False
-
-    def cover_writes(self, actor) -> None:
-        """Keep the pre-sampled batch across the steps of ``actor``, a serial ``BatchedActor`` on
-        this engine's replay that clears its starts ``clear_ahead`` rows ahead of its write head
-        (actor.hip, ahead > 0): up to ``clear_ahead`` of its steps between two learner steps
-        overwrite no window of a batch sampled before them (``_hoist_fresh``).  From now on every
-        hoisted step body begins with the device guard (replay.hip hoist_guard_kernel), which
-        recounts that claim from the actor's device step counter and write head and reports torn
-        pre-sampled windows in bit 29 of ``error_word``.  Call before ``capture``."""
-        if getattr(self, "graph", None):
-            raise RuntimeError("cover_writes() must be called before capture(): the guard is a node "
-                               "of every captured step")
-        if actor.replay is not self.replay:
-            raise ValueError("cover_writes: the actor writes another replay")
-        if int(getattr(actor, "clear_ahead", 0)) <= 0:
-            raise ValueError("cover_writes: the actor does not clear ahead (actor.clear_ahead > 0)")
-        if actor.defer:
-            raise ValueError("cover_writes: a deferred actor is covered by the concurrent driver")
-        if not self.hoist:
-            raise ValueError("cover_writes: this engine does not hoist (learner.hoist and its "
-                             "conditions, _hoist_ok)")
-        d = self.device
-        self._cover = dict(actor=actor, head=actor.head_d, t=actor.t_d, A=int(actor.clear_ahead),
-                           t_seen=actor.t_d.clone(),
-                           err=torch.zeros(2, dtype=torch.int32, device=d))
-        self.invalidate_hoist()
-
-    def _guard(self, presampled: bool) -> None:
-        """First operation of a hoisted step body once ``cover_writes`` was called: count the
-        slots of the batch in use whose windows the covered actor's steps since the previous
-        learner step overwrote (only when the batch was ``presampled``), refresh the snapshot."""
-        c = self._cover
-        if c is None:
-            return
-        rp = self.replay
-        check(kernels().r2_hoist_guard(ptr(self.starts), self.B, ptr(c["head"]), ptr(c["t"]),
-                                       ptr(c["t_seen"]), rp.cap_e, rp.n_sub, self.T, self.n,
-                                       ptr(rp.done), int(presampled), ptr(c["err"]), stream_handle()),
-              "hoist_guard")
-
-    def guard_count(self) -> int:
-        """Pre-sampled slots the guard found torn or in bootstrap violation so far (one D2H read;
-        0 without ``cover_writes``)."""
-        return int(self._cover["err"][1].item()) if self._cover is not None else 0
-
-    def _note_presample(self) -> None:
-        """Host state of the moment the next step's batch was sampled (``_hoist_fresh``)."""
-        rp = self.replay
-        self._hoist_gen = rp.total_written
-        if self._cover is not None:
-            self._hoist_unc = rp.total_written - rp.covered_written
-            self._hoist_t = self._cover["actor"].t
-
-    def _hoist_fresh(self) -> bool:
-        """The previous step sampled this step's batch AND the replay has not been written since
-        (every host-side writer bumps ``HBMReplay.total_written``): a batch sampled before a write
-        may hold windows the write overwrote, and came from a tree the plain step would not have
-        used.  ``writes_covered``: a driver whose writes stay clear of every batch that may
-        still be pending (engine/concurrent.py: lookahead >= 2 rounds) vouches for them.
-        ``cover_writes``: no uncovered write (``total_written - covered_written`` has not moved)
-        and at most ``clear_ahead`` steps of the covered actor."""
-        if not getattr(self, "_hoist_ready", False):
-            return False
-        rp = self.replay
-        if self.writes_covered or getattr(self, "_hoist_gen", None) == rp.total_written:
-            return True
-        c = self._cover
-        return bool(c is not None
-                    and getattr(self, "_hoist_unc", None) == rp.total_written - rp.covered_written
-                    and 0 <= c["actor"].t - self._hoist_t <= c["A"])
-
-    def _due(self, k: int) -> bool:
-        iv = int(self.cfg.learner.target_update_interval)
-        return iv <= 1 or (k + 1) % iv == 0
-
-    def _baked_interval(self) -> int:
-        """The target-sync interval handed to the update / pack kernels: the hoisted step's graph
-        variants bake the due decision (1 = due, 2^62 = never), so the device step counter --
-        already advanced by the side stream's priority tail -- is not read for it."""
-        if not self.hoist:
-            return int(self.cfg.learner.target_update_interval)
-        return 1 if self._hoist_due else 1 << 62
-
-    def _step_off(self) -> int:
-        """Adam's step count is the device step counter + this: 1 in the plain and DP steps (the
-        update runs before the counter advances), 0 in the hoisted step (the side branch's priority
-        tail, joined before the update, already advanced it)."""
-        return 0 if self.hoist else 1
-
-    def _side_stream(self):
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        return self._side
-
     def _hoist_side(self, torso: bool, after_td, td_wait: bool = False):
         """The side branch, forked at event ``after_td`` (recorded right after the TD launch):
         priority tail(k) + step counter, sample(k+1) into the other set (zeroing the frame
@@ -664,218 +501,6 @@ class LearnerEngine:
     def _bptt_groups_wgs(self) -> int:
         """Workgroups of the BPTT recurrence (batch tiles x hidden / 16)."""
         return -(-self.B // 16) * (self.layout.H // UNITS)
-
-    def _hoist_body(self, p: int, inm: str, due: bool):
-        """The hoisted step as stream operations (eager or captured): sample set ``p``; ``inm``
-        'P' = sample at the start (no previous hoisted step), 'H' = the previous step sampled;
-        ``due``: this step's update syncs the target (no target frames hoisted for the next
-        step: they would use the old target weights)."""
-        self._use_set(p)
-        self._hoist_due = due
-        self._guard(inm == "H")
-        if inm == "P":
-            self._sample(qreset=self.tq)
-        self._hoist_td_side(due, self._forward_rest)
-        self._seg_torso()
-        self._update()
-
-    def _hoist_td_side(self, due: bool, fwd, before_join=None):
-        """The middle of a hoisted step: ``fwd`` (the forward up to and including the TD launch),
-        the BPTT + post-BPTT group, the side branch forked at the TD launch, and the join.
-        ``before_join`` (the DP step): issued on the main stream after the side branch and before
-        the join -- the core gradient bucket's all-reduce start."""
-        early = (bool(self.cfg.learner.hoist_early_fork) and self.td_done is not None
-                 and not getattr(self, "_early_refused", False) and not _dispatch_serialized())
-        if early:
-            # fork before the TD launch (the side queue's start latency, ~13 us after its fork
-            # event, then overlaps TD); the priority tail waits for TD's done flag on the device
-            self._early_fork = torch.cuda.Event()
-            self._early_post = None
-        try:
-            fwd()
-        finally:
-            after_td, self._early_fork = getattr(self, "_early_fork", None), None
-        # (the fork is recorded only by the fused TD + head launch, td_fuse_head_bwd; without it
-        # the side branch forks after TD as before)
-        early = early and getattr(self, "_early_post", None) is not None
-        main = torch.cuda.current_stream(self.device)
-        if not early:
-            after_td = torch.cuda.Event()
-            after_td.record(main)
-        # the BPTT and the weight-gradient group are issued (captured) BEFORE the side branch:
-        # the graph keeps the first dependent of the TD node on the TD's queue, so the critical
-        # path does not pay a cross-queue hand-off (measured: the BPTT started 11 us after the TD
-        # when the side branch was captured first)
-        self._backward_core()
-        side = self._hoist_side(torso=not due, after_td=after_td, td_wait=early)
-        # join before the conv backward: the side branch ends with the BPTT (joining at the end of
-        # the step instead let the side torso slow the conv backward: measured slower)
-        if before_join is not None:
-            before_join()
-        main.wait_stream(side)
-
-    # ---- the hoisted step on data-parallel ranks (dist.hoist_dp).  The serial DP step runs the
-    # priority tail beside the torso bucket's all-reduce and the counter after the update; here the
-    # tail, the counter, the next sample and its shard stats (replay.hip r2_prio_tail_sample_dp) are
-    # the side branch, so the shard stats become part of the sample set: an 'H' step's all-gather
-    # reads what the previous step's side branch wrote, a 'P' step's what its own sample wrote.
-    # The all-gather stays at the step start beside the forward and no collective runs on the side
-    # branch: whichever variant a rank replays (ranks decide _hoist_fresh on their own replay), it
-    # issues the collectives of ``dp_hoist_plan`` in the same order and meets its peers at each.
-    def _gather_fork(self):
-        """The shard-stats all-gather of the set in use on its own stream, forked from the main
-        stream here (joined by ``_gather_join`` before the heads / TD)."""
-        main = torch.cuda.current_stream(self.device)
-        if getattr(self, "_gather_stream", None) is None:
-            self._gather_stream = torch.cuda.Stream(device=self.device)
-        gs = self._gather_stream
-        gs.wait_stream(main)
-        with torch.cuda.stream(gs):
-            self._gather_dp()
-
-    def _gather_join(self):
-        torch.cuda.current_stream(self.device).wait_stream(self._gather_stream)
-
-    def _hseg_sample(self):            # 'P' only: guard (no pre-sampled batch to check) + sample
-        self._guard(False)
-        self._sample(qreset=self.tq)   # (+ the local shard stats into the set, dp_global)
-
-    def _hseg_fwd_head(self, presampled: bool):
-        if presampled:
-            self._guard(True)
-        self._forward_rest(tail=False)
-
-    def _hseg_core_side(self, due: bool, before_join=None):
-        self._hoist_td_side(due, self._forward_tail, before_join)
-
-    def _hseg_update(self):            # (the side branch's tail already advanced the counter)
-        self._update()
-
-    def _hoist_dp_body(self, p: int, inm: str, due: bool):
-        """The hoisted DP step as stream operations (eager, or captured as the one graph with the
-        collectives on their streams).  The segments and collectives of ``dp_hoist_plan`` in its
-        order, except that the core bucket's all-reduce starts before the side branch is joined
-        (inside one capture that is an edge; between segment graphs it cannot be)."""
-        L = self.layout
-        self._use_set(p)
-        self._hoist_due = due
-        if inm == "P":
-            self._hseg_sample()
-        if self.dp_global:
-            self._gather_fork()
-        self._hseg_fwd_head(inm == "H")
-        if self.dp_global:
-            self._gather_join()
-        self._hseg_core_side(due, lambda: self._sync().start(0, L.torso_offset))
-        self._seg_torso()
-        self._sync().start(L.torso_offset, L.padded)
-        self._sync().finish()
-        self._hseg_update()
-
-    def _hoist_dp_segments(self, p: int, inm: str, due: bool):
-        """The hoisted DP step as segment graphs with the collectives issued by the host between
-        them (gloo; the dist.one_graph_warm steps; after a rollout fallback), driven by
-        ``dp_hoist_plan``."""
-        L = self.layout
-        self._use_set(p)
-        self._hoist_due = due
-        key = {"sample": (p,), "fwd_head": (p, inm), "core_side": (p, due), "torso": (p,),
-               "update": (due,)}
-        coll = {"all_gather": self._gather_fork,
-                "all_reduce_core": lambda: self._sync().start(0, L.torso_offset),
-                "all_reduce_torso": lambda: (self._sync().start(L.torso_offset, L.padded),
-                                             self._sync().finish())}
-        for kind, name in dp_hoist_plan(self.dp_global, inm):
-            if kind == "collective":
-                coll[name]()
-                continue
-            if name == "core_side" and self.dp_global:
-                self._gather_join()
-            self._hsegs[(name,) + key[name]].replay()
-
-    def _capture_hoist_dp(self):
-        """Every segment graph ``_hoist_dp_segments`` can ask for: sample (set), forward up to the
-        heads (set x 'P' / 'H': the guard checks a pre-sampled batch), heads + TD + BPTT + side
-        branch + join (set x due), torso backward (set), update (due)."""
-        self._hsegs, pool = {}, None
-        cur, due0 = self._cur, getattr(self, "_hoist_due", False)
-        todo = [(("sample", p), self._hseg_sample, ()) for p in (0, 1)]
-        todo += [(("fwd_head", p, i), self._hseg_fwd_head, (i == "H",)) for p in (0, 1) for i in "PH"]
-        todo += [(("core_side", p, d), self._hseg_core_side, (d,)) for p in (0, 1) for d in (False, True)]
-        todo += [(("torso", p), self._seg_torso, ()) for p in (0, 1)]
-        todo += [(("update", d), self._hseg_update, ()) for d in (False, True)]
-        for key, fn, args in todo:
-            if key[0] != "update":
-                self._use_set(key[1])
-            self._hoist_due = bool(key[-1]) if key[0] in ("core_side", "update") else False
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=self._capture_mode()):
-                fn(*args)
-            pool = g.pool()
-            self._hsegs[key] = g
-            self.graphs.append(g)
-        self._use_set(cur)
-        self._hoist_due = due0
-
-    def _hoist_step(self):
-        k = self.steps_done
-        if getattr(self, "_dev_step_off", None) is None:
-            self._dev_step_off = int(self.replay.step.item()) - k
-        due = self._due(k + self._dev_step_off)
-        p = k & 1
-        inm = "H" if self._hoist_fresh() else "P"
-        if self.dp:
-            if not self.graph:
-                self._hoist_dp_body(p, inm, due)
-            elif self._rollout.mode == "one":
-                self._use_set(p)
-                self._hoist_due = due
-                self._one_graphs[(p, inm, due)].replay()
-            else:
-                self._hoist_dp_segments(p, inm, due)
-        elif self.graph:
-            self._use_set(p)
-            self._hgraphs[(p, inm, due)].replay()
-        else:
-            self._hoist_body(p, inm, due)
-        self.hoisted_steps += inm == "H"
-        self._hoist_ready = True
-        self._note_presample()                         # the replay the next batch was sampled from
-        self.steps_done += 1
-        if self.dp and self.graph:
-            self._dp_rollout_after_step()
-
-    def _chunk_len(self) -> int:
-        if not self.hoist or self.dp:     # (no multi-step chunk graph at DP: run_steps -> step)
-            return 1
-        return max(1, int(getattr(self.cfg.learner, "graph_chunk", 1)))
-
-    def run_steps(self, n: int) -> None:
-        """``n`` learner steps, the same work and results as ``n`` calls of ``step``.  In the
-        hoisted graph mode a run of ``learner.graph_chunk`` steps that starts at an even step,
-        follows a hoisted step with no replay write since (``_hoist_fresh``; writes happen between
-        calls, so never inside a chunk) and has no target sync inside replays as ONE captured graph
-        (the hoisted bodies back to back on the same streams): the ~5 us boundary between two
-        graph replays (profiles/r06_step_timeline.txt) is paid once per chunk."""
-        m = self._chunk_len()
-        while n > 0:
-            k = self.steps_done
-            off = getattr(self, "_dev_step_off", None)
-            if (n >= m and m > 1 and self.graph and getattr(self, "_cgraph", None) is not None
-                    and (k & 1) == 0 and self._hoist_fresh() and off is not None
-                    and not any(self._due(k + j + off) for j in range(m))):
-                self._use_set(0)
-                self._cgraph.replay()
-                self.chunks_run = getattr(self, "chunks_run", 0) + 1
-                self._use_set((m - 1) & 1)
-                self._hoist_due = False
-                self.hoisted_steps += m
-                self._note_presample()
-                self.steps_done += m
-                n -= m
-            else:
-                self.step()
-                n -= 1
 
     def state_dict(self):
         return self.layout.state_dict(self.master)
@@ -1214,7 +839,7 @@ class LearnerEngine:
             fuse_dh = lc.td_fuse_dh and L.H == 256 and not self._dh_in_bptt()
             w1t = ptr(pk["head1T"]) if fuse_dh else 0
             w1t_lo = ptr(self.pk_lo["head1T"]) if fuse_dh and self.sp else 0
-            ef = getattr(self, "_early_fork", None)
+            ef = self._early_fork
             if ef is not None:
                 # hoisted step, early fork: the side branch forks here, before the TD launch, and
                 # its priority tail waits on the device for this launch's done flag
@@ -1332,7 +957,7 @@ class LearnerEngine:
         if Lb >= 1:
             h_prev, h_prev_l = hs[Lb - 1: T - 1].reshape(N, H), hl[Lb - 1: T - 1].reshape(N, H)
         else:   # the stored h0 (fp32) -> a split pair, then the chain's outputs
-            if getattr(self, "_hprev_sp", None) is None:
+            if self._hprev_sp is None:
                 self._hprev_sp = torch.zeros(2, N, H, dtype=torch.bfloat16, device=self.device)
             h0 = self.h0["on"]
             hi0 = h0.to(torch.bfloat16)
@@ -1460,7 +1085,7 @@ class LearnerEngine:
         if len(splits) != 4 or any(p.a.shape[1] % 64 for p in probs):
             return None
         need = group_ws_bytes(probs, splits)
-        if getattr(self, "gg_ws", None) is None or self.gg_ws.numel() * 4 < need:
+        if self.gg_ws is None or self.gg_ws.numel() * 4 < need:
             if torch.cuda.is_current_stream_capturing():
                 return None
             self.gg_ws = torch.zeros(need // 4 + 1, dtype=torch.float32, device=self.device)
@@ -1608,7 +1233,7 @@ class LearnerEngine:
         L.view(g, "vis_layers.0.bias").copy_(db1)
 
     def _update(self):
-        assert getattr(self, "_pack_deferred", None) is None, \
+        assert self._pack_deferred is None, \
             "a deferred weight repack was never run (_update without _priorities after it)"
         k = kernels()
         s = stream_handle()
@@ -1618,7 +1243,7 @@ class LearnerEngine:
         clip = 0
         # the torso backward left its slabs (``_backward_torso(defer_reduce=True)``): the first
         # launch below that reads the torso gradient sums them
-        slabs = self._fold_tq is not None and getattr(self, "_torso_deferred", False)
+        slabs = self._fold_tq is not None and self._torso_deferred
         lo_off = L.bf_numel if self.sp else 0
         if lc.grad_clip > 0:
             # fixed-order sum of squares (the same bits every run and on every DP rank), with the
@@ -1686,7 +1311,7 @@ class LearnerEngine:
 
     def _priorities(self, end: bool = True):
         rp = self.replay
-        deferred = getattr(self, "_pack_deferred", None)
+        deferred = self._pack_deferred
         self._pack_deferred = None
         if deferred is not None:
             head, tail = self._pack_args(*deferred)
@@ -1704,356 +1329,6 @@ class LearnerEngine:
             rp.step_end()
 
     # ------------------------------------------------------------------ public API
-    def _sync(self):
-        if getattr(self, "_gsync", None) is None:
-            from ..parallel.grad_sync import GradSync
-            self._gsync = GradSync(self.grad, self.world, self.pg, self.cfg.dist.grad_dtype,
-                                   use_stream=self.cfg.dist.overlap_allreduce, force=self.dp)
-        return self._gsync
-
-    def _seg_core(self):
-        self._forward_loss()
-        self._backward_core()
-
-    # DP with global sampling: the sampled batch's shard stats are all-gathered between the
-    # sampling launch and the rest of the forward
-    def _seg_sample(self):
-        self._sample()
-
-    def _seg_core_rest(self):
-        self._forward_rest()
-        self._backward_core()
-
-    def _seg_fwd_head(self):       # DP global sampling: everything before the TD (gather in flight)
-        self._forward_rest(tail=False)
-
-    def _seg_core_tail(self):      # ... and from the heads / TD on (gathered stats joined)
-        self._forward_tail()
-        self._backward_core()
-
-    def _seg_torso(self):
-        # the update that follows (same segment) sums the slabs itself when folded
-        self._backward_torso(defer_reduce=self._fold_tq is not None)
-
-    def _seg_tail(self):
-        self._update()
-        self._priorities()
-
-    def _single_body(self, timer=None, _presampled: bool = False):
-        """The world == 1 step as stream operations (eager or captured).  (Running the priority
-        refresh + tree repair on a side stream beside the BPTT was measured neutral and removed:
-        profiles/r03_prio_side_stream_ab.txt.)"""
-        import contextlib
-        ph = timer.phase if timer is not None else (lambda name: contextlib.nullcontext())
-        with ph("forward+td"):
-            self._forward_loss(_presampled)
-        with ph("backward_core"):
-            self._backward_core()
-        with ph("backward_torso"):
-            self._seg_torso()
-        with ph("update"):
-            self._update()
-        with ph("priorities"):
-            self._priorities()
-
-    # DP (world > 1): the priority refresh + tree repair need only the forward's TD errors, so
-    # they run while the torso bucket is all-reduced; the update and the step counter follow
-    def _seg_prio(self):
-        self._priorities(end=False)
-
-    def _seg_update(self):
-        self._update()
-        self.replay.step_end()
-
-    def step_eager(self, timer=None, _presampled: bool = False):
-        """One step without the graph.  ``timer``: optional utils.profiling.PhaseTimer -- every
-        phase is bracketed by HIP events and a roctx range (bench.py --profile-phases).
-        ``_presampled`` (private, plain single-rank step only): the caller already sampled this
-        step's batch with ``_sample()``, so the step does not sample at its start."""
-        import contextlib
-        L = self.layout
-        ph = timer.phase if timer is not None else (lambda name: contextlib.nullcontext())
-        if _presampled and (self.hoist or self.dp):
-            raise ValueError("_presampled: the plain single-rank step only")
-        if self.hoist:     # (no per-phase timer: the step's phases overlap on two streams)
-            g, self.graph = self.graph, None
-            try:
-                self._hoist_step()
-            finally:
-                self.graph = g
-            return
-        if not self.dp:
-            self._single_body(timer, _presampled)
-            self.steps_done += 1
-            return
-        with ph("forward+td"):
-            self._forward_loss()      # (DP global sampling: includes the stats all-gather)
-        with ph("backward_core"):
-            self._backward_core()
-        self._sync().start(0, L.torso_offset)        # core bucket: overlaps the conv backward
-        with ph("backward_torso"):
-            self._seg_torso()
-        self._sync().start(L.torso_offset, L.padded)  # torso bucket: overlaps the priority tail
-        with ph("priorities"):
-            self._seg_prio()
-        with ph("allreduce_wait"):
-            self._sync().finish()
-        with ph("update"):
-            self._seg_update()
-        self.steps_done += 1
-
-    def capture(self, warmup: int = 2):
-        """Capture the step into HIP graphs.  world == 1: one graph for the whole step (hoisted:
-        one per variant).  world > 1 with dist.hoist_dp: the hoisted DP step's segment graphs
-        (``_capture_hoist_dp``: sample | forward to the heads | TD + BPTT + side branch + join |
-        conv bwd | update, every (sample set, 'P' / 'H', due) variant a step can ask for, none
-        captured inside a step loop), the collectives issued between them as ``dp_hoist_plan``
-        orders them; the one graph per variant follows after dist.one_graph_warm steps (RCCL).
-        world > 1 otherwise: four graphs (core fwd/bwd | conv bwd | priorities | update) with the two
-        bucket all-reduces issued between them on the communication stream; with global
-        sampling the core graph is split after the sampling launch and again before the heads /
-        TD (six graphs): the 12-byte shard-stats all-gather runs on its own stream beside the
-        torso / x-projection / LSTM graph and is joined before the TD."""
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.step_eager()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        self.graphs = []
-        self._one_dp_graph = False
-        if self.hoist and self.dp:
-            # the hoisted DP step (dist.hoist_dp): the segment graphs of every variant now; the one
-            # graph per variant replaces them after dist.one_graph_warm steps (RCCL only)
-            self._make_rollout()
-            self._cgraph = None
-            self._capture_hoist_dp()
-            torch.cuda.synchronize(self.device)
-            self.graph = True
-            return
-        if self.hoist:
-            # the hoisted step's graph variants: (sample set, sampled by the previous step or
-            # not, target sync due) -- all eight captured now, none inside a timed loop
-            self._hgraphs, self._hpool = {}, None
-            cur, due = self._cur, getattr(self, "_hoist_due", False)
-            for key in [(p, i, d) for p in (0, 1) for i in ("H", "P") for d in (False, True)]:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self._hpool):
-                    self._hoist_body(*key)
-                if self._hpool is None:
-                    self._hpool = g.pool()
-                self._hgraphs[key] = g
-            # runs of graph_chunk steps starting at an even step, none due, previous step sampled
-            # (run_steps): one graph, so the inter-replay boundary is paid once per chunk
-            self._cgraph = None
-            m = self._chunk_len()
-            if m > 1:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self._hpool):
-                    for j in range(m):
-                        self._hoist_body(j & 1, "H", False)
-                self._cgraph = g
-                _graph_upload(g)
-            self._use_set(cur)
-            self._hoist_due = due
-            torch.cuda.synchronize(self.device)
-            self.graph = True
-            return
-        if self.dp:
-            self._make_rollout()
-        if self.dp:
-            segs = [self._seg_core, self._seg_torso, self._seg_prio, self._seg_update]
-            if self.dp_global:
-                segs = [self._seg_sample, self._seg_fwd_head, self._seg_core_tail] + segs[1:]
-        else:
-            segs = [self._single_body]
-        pool = None
-        for fn in segs:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=self._capture_mode()):
-                fn()
-            pool = g.pool()
-            self.graphs.append(g)
-        torch.cuda.synchronize(self.device)
-        self.graph = True
-
-    def _make_rollout(self) -> None:
-        """The segment graphs first; the whole DP step as ONE graph (collectives captured on their
-        side streams) replaces them after dist.one_graph_warm steps and, at world > 1, a
-        validation window (parallel/graph_rollout.py)."""
-        from ..parallel.graph_rollout import GraphRollout
-        dc = self.cfg.dist
-        one = dc.graph_collectives and (self.world == 1 or dc.graph_collectives_multi)
-        self._rollout = GraphRollout(self.pg, self.rank, self.world,
-                                     enabled=one and self._pg_backend() == "nccl",
-                                     warm=int(dc.one_graph_warm), validate=int(dc.one_graph_validate),
-                                     device=self.device)
-
-    def _capture_mode(self) -> str:
-        """Graph capture error mode: with a process group the RCCL watchdog thread polls the events
-        of earlier collectives while this thread captures, which global mode turns into a capture
-        error (hipErrorStreamCaptureUnsupported on the watchdog, seen as a flaky forced-DP test);
-        thread-local mode confines the capture rules to this thread."""
-        return "thread_local" if self.dp else "global"
-
-    def _pg_backend(self) -> str:
-        """Backend of the DP process group (only RCCL collectives can be graph-captured; gloo
-        ones -- CPU tests, ranks sharing a GPU -- stay between segment graphs)."""
-        import torch.distributed as dist
-        try:
-            return str(dist.get_backend(self.pg))
-        except (RuntimeError, ValueError):
-            return ""
-
-    def _dp_step_body(self):
-        """The DP step as stream operations (capturable): segments in order, the collectives on
-        their side streams with event fork / join -- what ``step`` issues between the segment
-        graphs."""
-        L = self.layout
-        if self.dp_global:
-            self._seg_sample()
-            main = torch.cuda.current_stream(self.device)
-            if getattr(self, "_gather_stream", None) is None:
-                self._gather_stream = torch.cuda.Stream(device=self.device)
-            gs = self._gather_stream
-            gs.wait_stream(main)
-            with torch.cuda.stream(gs):
-                self._gather_dp()
-            self._seg_fwd_head()
-            main.wait_stream(gs)
-            self._seg_core_tail()
-        else:
-            self._seg_core()
-        self._sync().start(0, L.torso_offset)
-        self._seg_torso()
-        self._sync().start(L.torso_offset, L.padded)
-        self._seg_prio()
-        self._sync().finish()
-        self._seg_update()
-
-    def _capture_one_dp(self) -> None:
-        """The whole DP step in ONE graph: the bucket all-reduces and the shard-stats all-gather
-        are captured on their side streams (fork / join as graph edges), so the ~15 us gap of
-        every segment boundary disappears.  The hoisted DP step (dist.hoist_dp): one such graph
-        per (sample set, 'P' / 'H', due) variant, the same collectives in the same order in each."""
-        torch.cuda.synchronize(self.device)
-        pool = self.graphs[0].pool() if self.graphs else None
-        if self.hoist:
-            # one graph per (sample set, 'P' / 'H', due) variant of the hoisted DP step
-            cur, due0 = self._cur, getattr(self, "_hoist_due", False)
-            gs = {}
-            try:
-                for key in [(p, i, d) for p in (0, 1) for i in ("H", "P") for d in (False, True)]:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, pool=pool, capture_error_mode=self._capture_mode()):
-                        self._hoist_dp_body(*key)
-                    gs[key] = g
-            finally:
-                self._use_set(cur)
-                self._hoist_due = due0
-            torch.cuda.synchronize(self.device)
-            self._one_graphs = gs
-            self._one_dp_graph = True
-            return
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=pool, capture_error_mode=self._capture_mode()):
-            self._dp_step_body()
-        torch.cuda.synchronize(self.device)
-        self._one_graph = g
-        self._one_dp_graph = True
-
-    def _dp_checksum(self) -> torch.Tensor:
-        """A fingerprint of this rank's weights (0-d float64, on the device): equal on every rank
-        while the ranks stay in lock-step."""
-        return self.master.double().sum() + 3.0 * self.target.double().sum()
-
-    def _dp_repair(self) -> None:
-        """After a one-graph validation mismatch: every rank takes rank 0's weights and optimizer
-        state, re-packs its kernel layouts and (hoisted DP step) drops the pre-sampled batch."""
-        import torch.distributed as dist
-        src = dist.get_global_rank(self.pg, 0) if hasattr(dist, "get_global_rank") else 0
-        for t in (self.master, self.target, self.opt_a, self.opt_b):
-            dist.broadcast(t, src=src, group=self.pg)
-        self._pack(always=True)
-        self._one_dp_graph = False
-        self.invalidate_hoist()     # the pre-sampled batch's target frames used the old weights
-
-    def _dp_rollout_after_step(self) -> None:
-        ro = getattr(self, "_rollout", None)
-        if ro is None:
-            return
-        if ro.validating():
-            if ro.record(self._dp_checksum(), self.err, self.steps_done) is False:
-                self._dp_repair()
-        elif ro.want_promote(self.steps_done):
-            err = None
-            try:
-                self._capture_one_dp()
-            except Exception as e:   # noqa: BLE001 -- the runtime refused the capture
-                err = "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:120] if str(e) else "")
-                self._one_graph, self._one_dp_graph = None, False
-                # host-side step state a half-captured body may have left behind
-                self._pack_deferred = None
-                self._gsync = None
-                torch.cuda.synchronize(self.device)
-            if ro.agree(err is None):
-                ro.promoted()
-            else:
-                self._one_graph, self._one_dp_graph = None, False
-                ro.refused(err or "on another rank")
-
-    def dp_graph_label(self) -> Optional[str]:
-        """How the DP step is replayed (bench.py JSON): segment graphs, the one graph (validated
-        or still validating), or the fallback after a mismatch; None without DP."""
-        if not self.dp:
-            return None
-        ro = getattr(self, "_rollout", None)
-        return ro.label() if ro is not None else "eager"
-
-    def step(self):
-        if self.hoist and self.graph:
-            self._hoist_step()
-            return
-        if not self.graph:
-            self.step_eager()
-            return
-        if not self.dp:
-            self.graphs[0].replay()
-        elif getattr(self, "_rollout", None) is not None and self._rollout.mode == "one":
-            self._one_graph.replay()
-            self.steps_done += 1
-            self._dp_rollout_after_step()
-            return
-        else:
-            L = self.layout
-            if self.dp_global:
-                g_sample, g_fwd, g_core, g_torso, g_prio, g_update = self.graphs
-                g_sample.replay()
-                # the shard-stats all-gather runs on its own stream beside the torso / LSTM graph
-                main = torch.cuda.current_stream(self.device)
-                if getattr(self, "_gather_stream", None) is None:
-                    self._gather_stream = torch.cuda.Stream(device=self.device)
-                gs = self._gather_stream
-                gs.wait_stream(main)
-                with torch.cuda.stream(gs):
-                    self._gather_dp()
-                g_fwd.replay()
-                main.wait_stream(gs)
-            else:
-                g_core, g_torso, g_prio, g_update = self.graphs
-            g_core.replay()
-            self._sync().start(0, L.torso_offset)
-            g_torso.replay()
-            self._sync().start(L.torso_offset, L.padded)
-            g_prio.replay()
-            self._sync().finish()
-            g_update.replay()
-            self.steps_done += 1
-            self._dp_rollout_after_step()
-            return
-        self.steps_done += 1
-
     def dp_imbalance(self) -> float:
         """W * sum_k (S_k / S)^2 of the last step's gathered shard totals: the variance inflation
         of the fixed-B shard-ratio sampling over one merged replay (parallel/sharded_replay.py;

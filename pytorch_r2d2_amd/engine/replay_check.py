@@ -1,7 +1,7 @@
 """Window-integrity oracle for a replay that is written while the learner samples from it.
 
 Pure host code (numpy).  A learner step trains on sequences it sampled earlier: at its own start
-(the plain step), or inside the previous step (the hoisted step, engine/learner_engine.py).  A
+(the plain step), or inside the previous step (the hoisted step, engine/step_driver.py).  A
 writer -- the batched actor, an ingest, the concurrent driver's actor round -- may overwrite ring
 rows between those two moments.  Given the sampled starts and, per learner step, the ring offsets
 written between the sampling of that step's batch and its training, ``check_windows`` reports

@@ -1,6 +1,6 @@
 """When may the data-parallel learner step run as ONE captured graph (collectives included)?
 
-The DP step has two captured forms (engine/learner_engine.py ``capture``):
+The DP step has two captured forms (engine/step_driver.py ``capture``):
 
     segments   4-6 graphs with the RCCL bucket all-reduces / the shard-stats all-gather issued
                between them on the communication stream -- the form the multi-rank tests pin;
@@ -11,7 +11,7 @@ The DP step has two captured forms (engine/learner_engine.py ``capture``):
 With ``dist.hoist_dp`` (the hoisted step on DP ranks) both forms exist per step variant -- (sample
 set, sampled at the step start or by the previous step's side branch, target sync due) -- with the
 priority segment folded into the side branch of the TD / BPTT segment; every variant issues the
-same collectives in the same order (engine/learner_engine.py ``dp_hoist_plan``), so ranks that
+same collectives in the same order (engine/step_driver.py ``dp_hoist_plan``), so ranks that
 replay different variants of one step still pair up, and this rollout promotes all variants at once.
 
 No multi-rank RCCL run has validated the one-graph form on this hardware, so it is rolled out per
