@@ -44,7 +44,7 @@ def build_parser():
     p.add_argument("--mode", choices=["compat", "native", "inproc", "eval"], default="compat")
     p.add_argument("--config", default=None, help="preset: reference|cartpole|pong|atari57|seaquest8|dmlab30")
     p.add_argument("--steps", type=int, default=None, help="learner steps (default: run forever in compat)")
-    p.add_argument("--env", default=None, help="override env name (synthetic|pong|cartpole)")
+    p.add_argument("--env", default=None, help="override env name (synthetic|pong|cartpole|pong_device|breakout_device)")
     p.add_argument("--device", default=None, help="learner device (compat/inproc)")
     p.add_argument("--actor-device", default="cpu", help="compat actors: cpu|cuda")
     p.add_argument("--metrics", default=None, help="JSONL metrics path")

@@ -24,7 +24,7 @@ from typing import Any, Dict, Optional
 
 @dataclass
 class EnvConfig:
-    name: str = "synthetic"          # synthetic | cartpole | pong | dmlab_synth | pong_device
+    name: str = "synthetic"          # synthetic | cartpole | pong | dmlab_synth | pong_device | breakout_device
     action_repeat: int = 4            # env.py:15
     n_stacks: int = 4                 # env.py:15
     frame_h: int = 84
@@ -43,6 +43,11 @@ class EnvConfig:
     pong_points: int = 21
     pong_max_steps: int = 5000
     pong_opp_lapse: int = 64
+    # breakout_device (the native Breakout-like game, breakout_ref.py): ``breakout_lives`` lives, at
+    # most ``breakout_max_steps`` agent steps, each shown plane blank with probability flicker/256
+    breakout_lives: int = 5
+    breakout_max_steps: int = 5000
+    breakout_flicker: int = 0
 
 
 @dataclass

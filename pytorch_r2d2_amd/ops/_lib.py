@@ -150,6 +150,8 @@ _SIGS = {
     "r2_synth_env_step": [P, P],
     "r2_pong_env_step": [P, P],
     "r2_pong_args_bytes": [],
+    "r2_breakout_env_step": [P, P],
+    "r2_breakout_args_bytes": [],
     "r2_stream_create_cumask": [P, I, P],
     "r2_stream_get_cumask": [P, P, I],
     "r2_stream_destroy": [P],

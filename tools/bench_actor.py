@@ -29,7 +29,7 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--set", nargs="*", default=[], metavar="KEY=VALUE",
-                    help="config overrides, e.g. env.name=pong_device")
+                    help="config overrides, e.g. env.name=pong_device or env.name=breakout_device")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     overrides = dict(kv.split("=", 1) for kv in args.set)
