@@ -79,6 +79,15 @@ class ReplayConfig:
     # ... and the sequence-priority refresh + level-0 repair in the same launch (grid barriers
     # between the levels, replay.hip prio_tail_kernel): the whole priority tail is one launch
     fused_prio_tail: bool = True
+    # stored recurrent states brought up to date from the learner's own forward pass (native
+    # learner, single rank; state_refresh_ref.py is the rule, state_refresh.hip the launch):
+    # "off" | "measure" = only report how far the stored states of the sampled windows have drifted
+    # from the states the current weights give (diagnostics() state_drift_*) | "write" = also
+    # write those states back into hs_cs / target_hs_cs, each row once
+    state_refresh: str = "off"
+    # chain steps a recomputed state must have behind it to be written or measured (0 .. burn_in +
+    # learn - 1); -1 = burn_in, so only states of the learning rows, with a full burn-in of context
+    state_refresh_context: int = -1
 
     @property
     def seq_len(self) -> int:

@@ -89,6 +89,41 @@ def torso_bwd_grid(n_frames: int, reserve_cus: int = 0, n_cus: int = 256) -> int
     return -(-n_frames // per)
 
 
+def state_refresh_plan(cfg: R2D2Config, dp: bool) -> Optional[Dict[str, object]]:
+    """replay.state_refresh resolved for one engine (None: off), or the refusal.  The rule is
+    state_refresh_ref.py's: ``context`` chain steps behind a state, ``o_tg`` the target chain's
+    first frame offset, ``shift`` 1 when the stored state is the one before the row's frame.
+
+    Why the write is safe under each driver -- the argument the priority tail already relies on,
+    which writes ``priority`` of the same windows' rows later in the step:
+      serial loop (runner.run_native, bench)  actor steps, ingests and learner steps are issued on
+        one stream, so the launch is ordered after every write of the rows it reads and before
+        every later reader; inside the step it sits on the main stream before the hoisted step's
+        fork, so the side branch's sample of the next batch sees it exactly as the next plain
+        step's sample would.
+      concurrent driver (engine/concurrent.py)  the actor writes rows only ``lookahead`` steps after
+        their starts were cleared and the clear applied in front of the learner step that could
+        still sample them, so no window of a batch in use (its T rows written here included) is a
+        row the actor writes beside the step.
+      ingest writers (HBMReplay.ingest_*, the split topology's links)  run on the host between two
+        learner steps on the learner's stream: stream order again.
+    Data-parallel ranks are refused: their step forms were not argued or tested."""
+    from ..state_refresh_ref import chain_offset, check_config, row_shift
+    rc, lc = cfg.replay, cfg.learner
+    ctx = check_config(rc.state_refresh, rc.state_refresh_context, rc.burn_in, rc.learn)
+    if rc.state_refresh == "off":
+        return None
+    if dp:
+        raise NotImplementedError("replay.state_refresh runs on the single-rank learner; "
+                                  "data-parallel engines refuse it")
+    if lc.zero_stored_state and rc.state_refresh == "write":
+        raise ValueError("replay.state_refresh=write with learner.zero_stored_state: the chains "
+                         "start from zeros, so the states written back would not continue the "
+                         "stored ones (measure is allowed)")
+    return dict(mode=rc.state_refresh, context=ctx, shift=row_shift(rc.stored_state),
+                o_tg=chain_offset("tg", lc.target_mode, rc.n_step))
+
+
 class LearnerEngine(StepDrivers):
     def _comm_reserve(self) -> int:
         dc = self.cfg.dist
@@ -106,6 +141,7 @@ class LearnerEngine(StepDrivers):
         # data-parallel step machinery: world > 1, or forced at world 1 (dist.force_dp rehearsal)
         self.dp = bool(process_group is not None and (world > 1 or cfg.dist.force_dp))
         m, e, rc, lc = cfg.model, cfg.env, cfg.replay, cfg.learner
+        self._refresh = state_refresh_plan(cfg, self.dp)     # None: replay.state_refresh off
         if m.torso != "atari":
             raise NotImplementedError("the HIP engine runs the conv torso (Atari / DMLab frames); "
                                       "use the torch learner for vector observations")
@@ -385,6 +421,17 @@ class LearnerEngine(StepDrivers):
         if lc.grad_clip > 0:
             self.gsq_part = z(int(kernels().r2_grad_sumsq_partials()))
             self.gsq_ticket = z(1, dt=torch.int32)
+        # stored-state refresh (state_refresh.hip): the drift words [on: sum dh^2, sum h^2, sum
+        # dc^2, sum c^2; tg: the same; rows on; rows tg; pad], per-workgroup partials and ticket
+        if self._refresh is not None:
+            if d.type != "cuda":
+                raise NotImplementedError("replay.state_refresh is a HIP launch: it needs a GPU engine")
+            if self.replay.cap_e < T or self.replay.H != H:
+                raise ValueError(f"replay.state_refresh: a sub-ring of {self.replay.cap_e} rows is "
+                                 f"shorter than the window of {T}, or the replay's hidden size differs")
+            self.sr_out = z(12)
+            self.sr_part = z(int(kernels().r2_state_refresh_partials()))
+            self.sr_ticket = z(1, dt=torch.int32)
         # DP global sampling: the all-gathered (W, 3) shard stats, TD's 4 parameters (the local
         # stats, dp_send, are part of the sample set above)
         self.dp_recv = z(max(1, self.world) * 3)
@@ -787,6 +834,8 @@ class LearnerEngine(StepDrivers):
         L, rp, lc = self.layout, self.replay, self.cfg.learner
         H, A = L.H, L.A
         pk, pt = self.pk, self.pk_t
+        if self._refresh is not None:
+            self._state_refresh()
         if self.dp_global:   # IS-weight parameters from the all-gathered shard stats
             if self.device.type == "cuda":     # one launch (dp_stats.hip)
                 check(kernels().r2_dp_is_params(ptr(self.dp_recv), self.world, self.rank,
@@ -871,6 +920,23 @@ class LearnerEngine(StepDrivers):
             if self.sp:
                 check(rc_, "td_duel")
         check(k.r2_td_loss(*targs, dp, s), "td_loss")
+
+    def _state_refresh(self):
+        """replay.state_refresh: one launch for both nets (state_refresh.hip; the rule:
+        state_refresh_ref.py).  First operation of ``_forward_tail``: every chain has run, and it
+        is on the main stream before the heads, so before the hoisted step's fork event -- the
+        side branch's sample of the next batch reads the replay after it, as the next plain
+        step's sample would (``state_refresh_plan``: why the write is safe under each driver).
+        Reads the sample set in use, like the TD launch."""
+        rf, rp, hl = self._refresh, self.replay, self.hseq_lo
+        on, tg = self.hseq["on"], self.hseq["tg"]
+        check(kernels().r2_state_refresh(
+            ptr(self.starts), self.B, self.layout.H, self.T, rp.cap_e, rp.capacity,
+            ptr(on), ptr(hl.get("on")), ptr(self.cseq["on"]), on.shape[0],
+            ptr(tg), ptr(hl.get("tg")), ptr(self.cseq["tg"]), tg.shape[0],
+            ptr(rp.hs_cs), ptr(rp.target_hs_cs), rf["o_tg"], rf["shift"], rf["context"],
+            int(rf["mode"] == "write"), ptr(self.sr_out), ptr(self.sr_part), ptr(self.sr_ticket),
+            stream_handle()), "state_refresh")
 
     def _dh_in_bptt(self) -> bool:
         """Split precision, hidden 256, head width 256: the BPTT computes its input gradient dh =
@@ -1355,11 +1421,23 @@ class LearnerEngine(StepDrivers):
         root = rp.tree[int(rp.tree_offs[-1]): int(rp.tree_offs[-1]) + 1]
         v = torch.stack([self.loss.reshape(()), q.mean(), q.max(1).values.mean(), q.max(),
                          td.mean(), td.max(), self.is_w.mean(), self.is_w.min(),
-                         root.reshape(()).float(), rp.n_valid.reshape(()).float()]).tolist()
+                         root.reshape(()).float(), rp.n_valid.reshape(()).float()])
+        if self._refresh is not None:      # the drift words ride on the same copy
+            v = torch.cat([v, self.sr_out[:10]])
+        v = v.tolist()
         keys = ("loss", "q_mean", "q_max_a_mean", "q_max", "td_abs_mean", "td_abs_max",
                 "is_w_mean", "is_w_min", "priority_sum", "n_valid")
         out = dict(zip(keys, v))
         out["replay_fill"] = rp.size / rp.capacity
+        if self._refresh is not None:
+            # how far the stored states of the rows the last step refreshed (or, "measure", would
+            # have) had drifted from the states the current weights give: sqrt(sum (new - old)^2 /
+            # sum new^2) over those rows, per net, for h and for c; state_rows: rows of both nets
+            s = v[len(keys):]
+            ratio = lambda a, b: (a / b) ** 0.5 if b > 0 else 0.0   # noqa: E731
+            out["state_drift_h"], out["state_drift_c"] = ratio(s[0], s[1]), ratio(s[2], s[3])
+            out["state_drift_h_tg"], out["state_drift_c_tg"] = ratio(s[4], s[5]), ratio(s[6], s[7])
+            out["state_rows"] = int(s[8] + s[9])
         if self.cfg.learner.grad_clip > 0:
             # the pre-clip global norm of the (rank-averaged) gradient of the step just taken
             out["grad_norm"] = float(self.clip_buf.item()) ** 0.5 / self.world

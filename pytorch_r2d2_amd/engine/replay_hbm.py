@@ -479,6 +479,25 @@ class HBMReplay:
                                float(rc.eta), ptr(self.n_valid), ptr(self.dirty),
                                ptr(self.dirty_count), self.max_dirty, stream_handle()), "mark_starts")
 
+    @torch.no_grad()
+    def set_hs_cs(self, rows, hs, cs, target_hs, target_cs) -> None:
+        """Scatter stored recurrent states into ``rows`` (the reference's ReplayMemory.set_hs_cs,
+        PARITY C16): one indexed copy per array on the device.  ``rows``:
+        distinct row indices; ``hs`` / ``cs`` / ``target_hs`` / ``target_cs``: (len(rows), H).  The
+        learner's own refresh of the rows it sampled is replay.state_refresh (state_refresh.hip)."""
+        idx = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.capacity):
+            raise ValueError("set_hs_cs: row outside the replay")
+        idx = idx.to(self.device)
+        vals = []
+        for t in (hs, cs, target_hs, target_cs):
+            t = torch.as_tensor(t, dtype=torch.float32).to(self.device)
+            if tuple(t.shape) != (idx.numel(), self.H):
+                raise ValueError(f"set_hs_cs: states must be ({idx.numel()}, {self.H}), got {tuple(t.shape)}")
+            vals.append(t)
+        self.hs_cs.index_copy_(0, idx, torch.cat(vals[:2], dim=1))
+        self.target_hs_cs.index_copy_(0, idx, torch.cat(vals[2:], dim=1))
+
     def flush_tree(self) -> None:
         """Repair the tree for all dirty leaves and reset the dirty list."""
         self.update_tree()

@@ -77,6 +77,8 @@ _SIGS = {
     "r2_torso_grad_reduce": [P, I, P, P, P, P],
     "r2_gather_state": [P, P, I, I, I, I, P, P, P, P],
     "r2_step_end": [P, P, P],
+    "r2_state_refresh": [P, I, I, I, I, I64, P, P, P, I, P, P, P, I, P, P, I, I, I, I, P, P, P, P],
+    "r2_state_refresh_partials": [],
     "r2_rmsprop_centered": [P, P, P, P, I64, F, F, F, F, P, F, P],
     "r2_rmsprop_pack": [P, P, P, P, I64, F, F, F, F, P, F, P, P, P, I64, P, P, I64, P],
     "r2_rmsprop_pack_slab": [P, P, P, P, I64, F, F, F, F, P, P, P, I64, P, P, I64, P, I, I, P, P, I64, P],

@@ -51,6 +51,8 @@ def parse(argv=None):
     ap.add_argument("--dtype", default="fp32", help="fp32 | bf16 | both")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--concurrent", action="store_true")
+    ap.add_argument("--state-refresh", default="off", choices=("off", "measure", "write"),
+                    help="replay.state_refresh: bring the stored states of the sampled windows up to date")
     return ap.parse_args(argv)
 
 
@@ -75,6 +77,7 @@ def make_cfg(args, dtype):
         ov["learner.zero_stored_state"] = True
         ov["actor.reset_state_every_step"] = True
         burn_in, learn, overlap = 0, 1, 1
+    ov["replay.state_refresh"] = args.state_refresh
     return get_config("atari57", **{
         "learner.compute_dtype": dtype, "seed": args.seed, "learner.batch_size": args.batch,
         "replay.burn_in": burn_in, "replay.learn": learn, "replay.overlap": overlap,
@@ -95,7 +98,9 @@ def run_one(args, dtype):
     windows = [round(float(rets[i:i + w].mean()), 2) for i in range(0, len(rets) - w + 1, w)]
     A = cfg.model.n_actions
     ceil = memoryless_ceiling(args.episode_len, args.switch, A) if args.memory else None
-    return {"metric": "synthetic_memory_task_return" if args.memory else "synthetic_cue_task_return",
+    extra = {"state_refresh": args.state_refresh} if args.state_refresh != "off" else {}
+    return {**extra,
+            "metric": "synthetic_memory_task_return" if args.memory else "synthetic_cue_task_return",
             "dtype": dtype, "seed": args.seed, "ablation": args.ablation,
             "switch": args.switch, "cue_only_first": bool(args.memory),
             "seq": [cfg.replay.burn_in, cfg.replay.learn], "batch": cfg.learner.batch_size,
